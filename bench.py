@@ -3,7 +3,7 @@
 Re_tau ~ 950 on the 1024 x 385 x 1024 grid (BASELINE.json), fp32 storage (fp64 y-solves), on N
 GPUs of one node with the slab decomposition (one rank per GPU, RCCL all-to-all over xGMI).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,8 +18,15 @@ Synthetic data: a seeded random divergence-free velocity field on a laminar mean
 (no checkpoint is available offline).  W untimed warm-up steps (the first one eager, then graph
 capture), then exactly K RK3 steps timed between barrier + device synchronisation on every rank;
 the MAX over ranks is reported.  Total work is fixed as N grows ("strong" scaling).  Per-step
-device times (hipEvents between graph launches) give the median and p90.  For P > 1 a few extra,
-untimed, eagerly-run steps with per-phase events give the exchange time and per-peer bandwidth.
+device times (hipEvents between graph launches) give the median and p90.
+
+A plain run does only that: set up, warm up, time the K steps, print the result line.
+``--dump-outputs DIR`` then writes what the last timed step left (the state a caller of the
+solver receives from ``get_state()``: phi, omega_y, the mean profile, and the step log) as
+``DIR/<name>.npy``; the initial condition is seeded, so two builds run with the same arguments
+can be compared output for output.  ``--full`` adds the measurements that take runs of their
+own: a few extra, untimed, eagerly-run steps with per-phase events (the phase times at any P;
+for P > 1 the exchange time and per-peer bandwidth).
 """
 from __future__ import annotations
 
@@ -50,6 +57,9 @@ STATS_EVERY = 10
 XGMI_LINK_GBPS = 153.0
 # slot 7: milliseconds in which a K-SPEC interval and an exchange interval ran at once (P > 1)
 PHASES = ["kspec", "x_backward", "z_physical", "x_forward", "a2a", "reduce", "io", "kspec_a2a_overlap"]
+# --dump-outputs: bytes per spectral field over all ranks (two fields; 64 MB is the limit for a dump)
+DUMP_FIELD_BYTES = 24 << 20
+DUMP_SEED = 20241
 
 
 def _free_port() -> int:
@@ -75,6 +85,31 @@ def _pct(v: list[float], q: float) -> float:
     return s[i]
 
 
+def _dump_outputs(solver, dirname: str, rank: int, world: int) -> None:
+    """Write the state after the last timed step as float64 .npy files (complex fields as
+    [..., (re, im)]).  A field larger than its share of DUMP_FIELD_BYTES is reduced to a fixed,
+    seeded sample of its elements (sorted flat indices of the local [y][kx][kz] block; the same
+    for every run of the same grid and rank count).  Ranks of a multi-GPU run write their own
+    blocks as <name>_rank<r>.npy."""
+    import numpy as np
+
+    phi, om, U = solver.get_state()
+    L = solver.log()
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    nmax = DUMP_FIELD_BYTES // 16 // world
+    for name, q in (("phi", phi), ("omega_y", om)):
+        q = np.ascontiguousarray(q, dtype=np.complex128)
+        if q.size > nmax:
+            idx = np.unique(np.random.default_rng(DUMP_SEED + rank).integers(0, q.size, size=nmax))
+            q = q.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), q.view(np.float64).reshape(q.shape + (2,)))
+    if rank == 0:
+        np.save(os.path.join(dirname, "U.npy"), np.asarray(U, dtype=np.float64))
+        np.save(os.path.join(dirname, "step_log.npy"),
+                np.array([L.time, L.dt, L.umax, L.vmax, L.wmax, L.utau], dtype=np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -86,8 +121,12 @@ def main() -> None:
     ap.add_argument("--decomposition", default="slab", choices=["slab", "pencil"])
     ap.add_argument("--pr", type=int, default=0, help="pencil rows (0 = automatic: the fewest bytes on the busiest link, 4x2 at 8 ranks)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state of the last one as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure (per-phase and exchange times)")
     ap.add_argument("--phases", action="store_true",
-                    help="after the timed steps, time a few more eagerly with per-phase hipEvents")
+                    help="after the timed steps, time a few more eagerly with per-phase hipEvents (part of --full)")
     ap.add_argument("--phase-steps", type=int, default=3)
     ap.add_argument("--stats-every", type=int, default=STATS_EVERY,
                     help="plane statistics every k-th step inside the timed region (0 = never)")
@@ -155,9 +194,11 @@ def main() -> None:
     p90 = max_over_ranks(_pct(step_ms, 0.9))
     graph = bool(solver.graph_active())
     L = solver.log()
+    if args.dump_outputs:
+        _dump_outputs(solver, args.dump_outputs, rank, world)
 
     phase = None
-    if args.phases or solver.comm_kind() != "none":
+    if args.phases or args.full:
         # untimed for the headline: eager steps with per-phase events (serialised at P = 1)
         solver.reset_phase_times()
         solver.set_phase_timing(True)

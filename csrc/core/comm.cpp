@@ -300,8 +300,12 @@ void ShmComm::alltoallv(const void* send, const std::vector<size_t>& scount, con
   HIP_CHECK(hipStreamSynchronize(s));
   if (scount[rank_]) {  // self block: device-to-device, never through host memory
     CH_CHECK(scount[rank_] == rcount[rank_], "alltoallv: self block send/recv sizes differ");
-    HIP_CHECK(hipMemcpy(static_cast<char*>(recv) + roff[rank_], static_cast<const char*>(send) + soff[rank_],
-                        scount[rank_], hipMemcpyDeviceToDevice));
+    // on the caller's stream and waited for: a device-to-device hipMemcpy runs on the null stream
+    // and may return before the copy is done, and the caller's (non-blocking) stream, on which it
+    // orders the consumers of recv, does not wait for the null stream
+    HIP_CHECK(hipMemcpyAsync(static_cast<char*>(recv) + roff[rank_], static_cast<const char*>(send) + soff[rank_],
+                             scount[rank_], hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   }
   for (int p = 0; p < size_; ++p) {
     if (p == rank_) continue;

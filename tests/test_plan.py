@@ -117,6 +117,45 @@ def test_bench_refuses_work_skipping_env(tmp_path):
     assert r.returncode != 0 and "work-skipping" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files of the state, a field larger than its share of
+    the 64 MB limit reduced to the same seeded sample in every run."""
+    import os
+    import sys
+    import types
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    try:
+        import bench
+    finally:
+        sys.path.remove(root)
+    n = bench.DUMP_FIELD_BYTES // 16
+    phi = (np.arange(3 * n, dtype=np.float64) * (1 + 0.5j)).reshape(3, n // 4, 4)
+
+    class FakeSolver:
+        def get_state(self):
+            return phi, 2 * phi, np.linspace(0.0, 1.0, 3)
+
+        def log(self):
+            return types.SimpleNamespace(time=0.5, dt=0.25, umax=1.0, vmax=2.0, wmax=3.0, utau=0.125)
+
+    for d in ("a", "b"):
+        bench._dump_outputs(FakeSolver(), str(tmp_path / d), 0, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["U.npy", "omega_y.npy", "phi.npy", "step_log.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    p, o = np.load(tmp_path / "a" / "phi.npy"), np.load(tmp_path / "a" / "omega_y.npy")
+    assert p.shape == o.shape and p.shape[1] == 2 and 0.5 * n < p.shape[0] <= n
+    # samples of phi itself, in index order: re = flat index, im = re / 2
+    assert np.all(np.diff(p[:, 0]) > 0) and np.array_equal(p[:, 1], 0.5 * p[:, 0]) and np.array_equal(o, 2 * p)
+
+
 def test_ny_cap_lifted_to_1536(native):
     """The reference's one-thread-per-y-point solver caps NY at 1024 (main.c:79-82); the register-
     resident y-line kernels go to R = 24 rows per lane (NY <= 1536), beyond which Plan refuses."""

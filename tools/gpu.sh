@@ -89,7 +89,7 @@ for step in "$@"; do
       run_cfg retau2000_fp32 400 --grid 2048x633x2048 --re 48300 --precision fp32 --steps 3 --warmup 1 ;;
     rehearse2)
       CHANNEL_COMM=shm CHANNEL_SHM_SLOT_MB=64 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --grid 256x129x256 \
+        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --grid 256x129x256 \
         --re 3250 --steps 3 --warmup 1 > $log 2>&1 || fail rehearse2 $log
       tail -n 1 $log ;;
     rehearse8)
@@ -98,7 +98,7 @@ for step in "$@"; do
       for dec in ${REHEARSE_DECS:-slab pencil pencil2x4}; do
         extra=""
         [ $dec = pencil2x4 ] && extra="--decomposition pencil --pr 2" || extra="--decomposition $dec"
-        CHANNEL_COMM=shm timeout -k 10 600 python bench.py --gpus 8 $extra --steps 2 --warmup 1 \
+        CHANNEL_COMM=shm timeout -k 10 600 python bench.py --full --gpus 8 $extra --steps 2 --warmup 1 \
           $BENCH_ARGS > gpurun_out/${tag}_rehearse8_$dec.log 2>&1 || fail "rehearse8 $dec" gpurun_out/${tag}_rehearse8_$dec.log
         tail -n 1 gpurun_out/${tag}_rehearse8_$dec.log
       done ;;
@@ -106,7 +106,7 @@ for step in "$@"; do
       # 2 and 4 ranks (slab: 4 and 2 kx sub-blocks, the K-SPEC / exchange overlap) on the one GPU
       # over the shared-memory loopback at the headline shape
       for n in 2 4; do
-        CHANNEL_COMM=shm CHANNEL_SHM_SLOT_MB=64 timeout -k 10 600 python bench.py --gpus $n --steps 2 --warmup 1 \
+        CHANNEL_COMM=shm CHANNEL_SHM_SLOT_MB=64 timeout -k 10 600 python bench.py --full --gpus $n --steps 2 --warmup 1 \
           $BENCH_ARGS > gpurun_out/${tag}_rehearse$n.log 2>&1 || fail "rehearse $n" gpurun_out/${tag}_rehearse$n.log
         tail -n 1 gpurun_out/${tag}_rehearse$n.log
       done ;;
