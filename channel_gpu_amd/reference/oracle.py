@@ -293,7 +293,9 @@ class OracleSolver:
 
     def __init__(self, NX, NY, NZ, Re=3250.0, Q=1.8, LX=2 * math.pi, LZ=math.pi, stretch=2.0, cfl=0.5,
                  dt_max=0.05, dt_fixed=0.0, P=1, rank=0, dist=None, Pr=1, explicit_d2="compact",
-                 influence="discrete"):
+                 influence="discrete", forcing="implicit"):
+        if forcing not in ("implicit", "parity"):
+            raise ValueError(f"forcing must be 'implicit' or 'parity', not {forcing!r}")
         self.plan = OraclePlan(NX, NY, NZ, P, rank, LX, LZ, Pr)
         self.ops = build_ops(NY, stretch)
         self.Re, self.nu, self.Q = Re, 1.0 / Re, Q
@@ -302,6 +304,10 @@ class OracleSolver:
         # reference-parity switches: explicit D2 as D1 o D1 (RK3_kernels.cu:160-164) and analytic
         # cosh/sinh influence functions (bilplacSolver_double.cu:56-250, l1/l2 typo fixed)
         self.explicit_d2, self.influence = explicit_d2, influence
+        # mean-flow forcing: "implicit" = exact flux through the implicit response to a uniform
+        # pressure gradient; "parity" = the reference's constant added to the interior points
+        # (meanUevol.c:201-221, COMPAT.md "mean forcing")
+        self.forcing = forcing
         p = self.plan
         shape = (NY, p.nkx_loc, p.nkz_loc)
         self.phi = np.zeros(shape, complex)
@@ -394,7 +400,8 @@ class OracleSolver:
         if p.P == 1:
             phys = spec_to_phys_full(F, p)
             H = rotational_product(phys)
-            self._maxima(phys, p.y0)
+            if compute_dt:  # (substep 0 only, like the GPU path: the maxima that chose dt stay readable)
+                self._maxima(phys, p.y0)
             self.H = phys_to_spec_full(H, p)
         else:
             cols = [p.rank_of(p.prow, c) for c in range(p.Pc)]   # A exchange: kx <-> y
@@ -411,7 +418,8 @@ class OracleSolver:
             Z = np.zeros((nf, p.ny_loc, p.nx_loc, p.NZ), complex)
             Z[..., :p.nkz] = np.concatenate([recv[g] for g in rows], axis=3)
             phys = np.fft.irfft(Z, n=p.Nzp, axis=-1, norm="forward")  # [6, ny_loc, nx_loc, Nzp]
-            self._maxima(phys, p.y0)
+            if compute_dt:
+                self._maxima(phys, p.y0)
             Hk = np.fft.rfft(rotational_product(phys), axis=-1, norm="forward")[..., :p.nkz]
             recv = self._a2a({g: Hk[..., p.kz_start[r]:p.kz_start[r] + p.kz_count[r]] for r, g in enumerate(rows)},
                              {g: (3, p.ny_loc, p.x_count[r], p.nkz_loc) for r, g in enumerate(rows)})
@@ -479,10 +487,17 @@ class OracleSolver:
         if m is not None:
             U1 = np.linalg.solve(Aimp[m], ops.M @ np.ones(ops.N))
             fU = ops.trap @ om_new[:, m].real
-            C = (self.Q - fU) / (ops.trap @ U1)
-            om_new[:, m] = om_new[:, m].real + C * U1
+            if self.forcing == "parity":
+                # half the flux defect (the channel is 2 high) on every interior row, walls untouched
+                C = (self.Q - fU) / 2.0
+                add = np.full(ops.N, C)
+                add[0] = add[-1] = 0.0
+            else:
+                C = (self.Q - fU) / (ops.trap @ U1)
+                add = C * U1
+            om_new[:, m] = om_new[:, m].real + add
             self.U = om_new[:, m].real.copy()
-            self.mean_C = C
+            self.mean_C, self.mean_flux, self.mean_U1 = C, fU, U1
         phi_p = _bsolve(Aimp, rP)
         L = phi_l.shape[1]
         e0 = np.zeros((ops.N, L))

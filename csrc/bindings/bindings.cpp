@@ -13,6 +13,7 @@
 #include <torch/extension.h>
 
 #include <complex>
+#include <cstring>
 #include <map>
 #include <memory>
 
@@ -219,17 +220,29 @@ torch::Tensor xfft_f_blocked(torch::Tensor phys, torch::Tensor specb, int rows, 
   return specb;
 }
 
-// z physical stage (tests): fields [6, ny, NX, nkz] -> H [3, ny, NX, nkz], maxima [4]
-std::pair<torch::Tensor, torch::Tensor> zphys_op(torch::Tensor fields, int Nzp, torch::Tensor inv_dy, double cx, double cz) {
+// z physical stage (tests): fields [6, ny, NX, nkz] -> H [3, ny, NX, nkz], maxima [4].  The planes
+// are rows y0 .. y0 + ny - 1 of the grid inv_dy describes (a chunk of a slab); maxima, when given,
+// is a float32[4] device tensor the kernel accumulates into (the solver's chunks share one)
+std::pair<torch::Tensor, torch::Tensor> zphys_op(torch::Tensor fields, int Nzp, torch::Tensor inv_dy, double cx, double cz,
+                                                 int y0, py::object maxima_in) {
   check_dev_tensor(fields, "fields");
   const bool f64 = is_fp64_complex(fields);
   TORCH_CHECK(fields.dim() == 4 && fields.size(0) == 6, "fields must be [6, ny, NX, nkz]");
   auto f = fields.clone();
   const int ny = f.size(1), NX = f.size(2), nkz = f.size(3);
-  auto maxima = torch::zeros({4}, fields.options().dtype(torch::kFloat32));
+  TORCH_CHECK(y0 >= 0 && inv_dy.dim() == 1 && inv_dy.numel() >= y0 + ny, "inv_dy must have at least y0 + ny entries");
+  torch::Tensor maxima;
+  if (maxima_in.is_none()) {
+    maxima = torch::zeros({4}, fields.options().dtype(torch::kFloat32));
+  } else {
+    maxima = maxima_in.cast<torch::Tensor>();
+    check_dev_tensor(maxima, "maxima");
+    TORCH_CHECK(maxima.scalar_type() == torch::kFloat32 && maxima.numel() == 4 && maxima.device() == fields.device(),
+                "maxima must be a float32[4] tensor on the fields' device");
+  }
   auto idy = inv_dy.to(fields.device(), torch::kFloat64).contiguous();
   ZArgs a;
-  a.NX = NX; a.Nzp = Nzp; a.nkz = nkz; a.ny = ny; a.y0 = 0;
+  a.NX = NX; a.Nzp = Nzp; a.nkz = nkz; a.ny = ny; a.y0 = y0;
   a.field_stride = static_cast<long long>(ny) * NX * nkz;
   a.scale = 1.0 / (static_cast<double>(NX) * Nzp);
   a.inv_dy = idy.data_ptr<double>();
@@ -237,6 +250,36 @@ std::pair<torch::Tensor, torch::Tensor> zphys_op(torch::Tensor fields, int Nzp, 
   a.maxima = maxima.data_ptr<float>();
   zphys(a, f.data_ptr(), twiddles(Nzp, f64), f64, cur_stream());
   return {f.narrow(0, 0, 3).contiguous(), maxima};
+}
+
+// time-step control kernel (tests): one dt_update on the given maxima, as the solver fills DtArgs
+// (dy_uniform = 2 / (NY - 1)); returns (dt_log[8], health, maxima after the call)
+py::tuple dt_update_op(torch::Tensor maxima, double cfl, double dt_max, double dt_fixed, int parity, int NX, int NZ,
+                       double LX, double LZ, double Re, int NY, double time0) {
+  TORCH_CHECK(maxima.numel() == 4, "maxima must have 4 entries");
+  TORCH_CHECK(NY >= 2, "NY must be at least 2");
+  auto dev = torch::TensorOptions().device(torch::kCUDA, c10::hip::current_device());
+  auto mx = maxima.to(dev.dtype(torch::kFloat32)).contiguous().clone();
+  // [0] dt, [1] time, [2..9] dt_log
+  auto hsc = torch::zeros({10}, torch::kFloat64);
+  hsc.data_ptr<double>()[1] = time0;
+  auto sc = hsc.to(dev.dtype(torch::kFloat64));
+  auto health = torch::zeros({1}, dev.dtype(torch::kInt32));
+  DtArgs a;
+  a.maxima = mx.data_ptr<float>();
+  a.dt = sc.data_ptr<double>();
+  a.time = a.dt + 1;
+  a.dt_log = a.dt + 2;
+  a.health = reinterpret_cast<unsigned*>(health.data_ptr<int>());
+  a.cfl = cfl; a.dt_max = dt_max; a.dt_fixed = dt_fixed; a.parity = parity;
+  a.NX = NX; a.NZ = NZ; a.LX = LX; a.LZ = LZ; a.Re = Re;
+  a.dy_uniform = 2.0 / (NY - 1);
+  dt_update(a, cur_stream());
+  auto h = sc.cpu();
+  // the solver's kernels read *dt and *time, the log reports dt_log[6], dt_log[7]: the same values
+  const double* hp = h.data_ptr<double>();
+  TORCH_CHECK(std::memcmp(hp, hp + 8, 2 * sizeof(double)) == 0, "dt_update: *dt, *time differ from dt_log[6], dt_log[7]");
+  return py::make_tuple(h.narrow(0, 2, 8).contiguous(), health.cpu().item<int>(), mx.cpu());
 }
 
 torch::Tensor field_tensor(Solver& s, int f) {
@@ -283,7 +326,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("combine") = 0, py::arg("ax") = 1.0, py::arg("az") = 2.0);
   m.def("xfft_forward_blocked", &xfft_f_blocked, py::arg("phys"), py::arg("specb"), py::arg("rows"), py::arg("y0"),
         py::arg("Kx"), py::arg("nt") = 0);
-  m.def("zphys", &zphys_op);
+  m.def("zphys", &zphys_op, py::arg("fields"), py::arg("Nzp"), py::arg("inv_dy"), py::arg("cx"), py::arg("cz"),
+        py::arg("y0") = 0, py::arg("maxima") = py::none());
+  m.def("dt_update", &dt_update_op, py::arg("maxima"), py::arg("cfl"), py::arg("dt_max"), py::arg("dt_fixed"),
+        py::arg("parity"), py::arg("NX"), py::arg("NZ"), py::arg("LX"), py::arg("LZ"), py::arg("Re"), py::arg("NY"),
+        py::arg("time0") = 0.0,
+        "one dt_update_kernel launch: (dt_log[8], health, maxima after the call)");
   m.def("xfft_last_variant", [] { return xfft_last_variant(); },
         "template arguments of the last x-transform launch (rocprofv3 kernel-name form)");
   m.def("xfft_last_backward_variant", [] { return xfft_last_backward_variant(); },

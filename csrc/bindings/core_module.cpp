@@ -119,6 +119,8 @@ PYBIND11_MODULE(_core, m) {
       .def("kx_fft_pos", &Plan::kx_fft_pos);
 
   m.def("yline_supported_R", &yline_supported_R);
+  m.def("kspec_last_variant", [] { return kspec_last_variant(); },
+        "kernel name(s) and template arguments of this thread's last K-SPEC launch (rocprofv3 kernel-name form)");
 
 
   m.def("new_unique_id", &new_uid);

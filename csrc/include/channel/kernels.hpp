@@ -127,6 +127,10 @@ struct SpecArgs {
 };
 constexpr int kKspecPhases = 10;
 void kspec_launch(const YTablesDev& t, const SpecArgs& a, bool fp64, hipStream_t stream);
+// kernel name(s) of this thread's last K-SPEC launch in rocprofv3's kernel-name form, template
+// arguments R, T, W, NS, XM, PAR, GLM, SPLIT, H ("kspec_kernel<7, float, 4, 2, 2, 0, 0, 0, 1>"); the
+// split (CHANNEL_KSPEC_SPLIT=1) reads "kspec_kernel<..., 1, 1> + kspec_out_kernel<R, T, W, XM>" (tests)
+std::string kspec_last_variant();
 
 // ---- FFT stages ---------------------------------------------------------------------------
 // Per-pass FFT twiddle tables for length n (FftPlan T1/T2 layout, fft_device.hpp), fp32 or fp64.

@@ -6,6 +6,23 @@ namespace channel {
 
 template void kspec_launch_par<0>(const YTablesDev&, const SpecArgs&, bool, hipStream_t);
 
+KspecVariant& kspec_variant_slot() {
+  static thread_local KspecVariant v;
+  return v;
+}
+std::string kspec_last_variant() {
+  const KspecVariant& v = kspec_variant_slot();
+  if (v.R == 0) return "";
+  const std::string ty = v.f64 ? "double" : "float";
+  std::string s = "kspec_kernel<" + std::to_string(v.R) + ", " + ty;
+  for (int x : {v.W, v.NS, v.XM, v.PAR, v.GLM, v.SPLIT, v.H}) s += ", " + std::to_string(x);
+  s += ">";
+  if (v.W2)
+    s += " + kspec_out_kernel<" + std::to_string(v.R) + ", " + ty + ", " + std::to_string(v.W2) + ", " +
+         std::to_string(v.XM) + ">";
+  return s;
+}
+
 void kspec_launch(const YTablesDev& t, const SpecArgs& a, bool fp64, hipStream_t stream) {
   CH_CHECK(a.N == t.tab.N, "kspec: NY mismatch with tables");
   CH_CHECK(!a.analytic_influence || a.ygrid, "kspec: analytic influence needs the y grid");

@@ -35,6 +35,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 
 #include "channel/common.hpp"
 #include "channel/fft_device.hpp"
@@ -1261,6 +1262,16 @@ static int kspec_split_env() {
   }();
   return v;
 }
+// one-time note when the switch cannot apply: the output kernel writes the combine outputs only, so
+// in the six-output mode (the one-rank default) the fused kernel runs
+static void kspec_split_ignored_note() {
+  static const bool noted = [] {
+    std::fprintf(stderr, "[channel] CHANNEL_KSPEC_SPLIT ignored: the split runs in the combine mode only "
+                         "(CHANNEL_COMBINE=1); this run is in the six-output mode\n");
+    return true;
+  }();
+  (void)noted;
+}
 template <int R, typename T>
 constexpr bool kspec_split_default() {
   // the instantiated split: fp32 storage, R = 5..7, where the output kernel is spill-free at two
@@ -1314,6 +1325,21 @@ static int kspec_var_env() {
   return v;
 }
 
+// The template arguments of this thread's last K-SPEC launch, as in the rocprofv3 kernel names
+// ("kspec_kernel<7, float, 4, 2, 2, 0, 0, 0, 1>"; the split adds " + kspec_out_kernel<...>"): tests
+// assert that a switch launched the variant it names.  Recorded as plain values on the launch
+// path and formatted only when asked for (kspec_last_variant, kspec.hip).
+struct KspecVariant {
+  int R = 0, W = 0, NS = 0, XM = 0, PAR = 0, GLM = 0, SPLIT = 0, H = 1;
+  int W2 = 0;  // lines per workgroup of the split's output kernel (0: one fused kernel)
+  bool f64 = false;
+};
+KspecVariant& kspec_variant_slot();
+template <int R, typename T>
+inline void kspec_note_variant(int W, int NS, int PAR, int GLM = 0, int SPLIT = 0, int H = 1, int W2 = 0) {
+  kspec_variant_slot() = KspecVariant{R, W, NS, static_cast<int>(kspec_xmode<R, T>()), PAR, GLM, SPLIT, H, W2, sizeof(T) == 8};
+}
+
 template <int R, typename T, int PAR = 0>
 static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t stream) {
   if constexpr (R == 3 && PAR == 0) {
@@ -1324,6 +1350,7 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
                : v == 4 ? kspec_kernel<3, T, 8, 5, kspec_xmode<3, T>(), 0>
                         : kspec_kernel<3, T, 8, 2, kspec_xmode<3, T>(), 0>;
       const int w = v == 1 ? W3 : 8;
+      kspec_note_variant<3, T>(w, v == 1 ? 1 : (v == 3 ? 7 : (v == 4 ? 5 : 2)), 0);
       const int nt = (a.lines + w - 1) / w;
       dim3 grid(std::min(nt, resident_blocks(reinterpret_cast<const void*>(k), w * 64))), block(w * 64);
       hipLaunchKernelGGL(k, grid, block, 0, stream, t.tab, a);
@@ -1335,6 +1362,7 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
       // lines over two waves: 4 lines x 2 halves = 8 waves per workgroup (two per SIMD)
       constexpr int W2 = 4;
       auto k = kspec_kernel<4, float, W2, kspec_slots<4, float>(), kspec_xmode<4, float>(), PAR, 0, 0, 2>;
+      kspec_note_variant<4, float>(W2, kspec_slots<4, float>(), PAR, 0, 0, 2);
       const int nt = (a.lines + W2 - 1) / W2;
       dim3 grid(std::min(nt, resident_blocks(reinterpret_cast<const void*>(k), W2 * 128))), block(W2 * 128);
       hipLaunchKernelGGL(k, grid, block, 0, stream, t.tab, a);
@@ -1344,12 +1372,21 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
   CH_CHECK(t.H == 1, "kspec: lines over two waves are instantiated for R = 4, fp32 storage");
   constexpr int W = kspec_lines<R, T>();
   auto kern = kspec_kernel<R, T, W, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR>;
+  int ns = kspec_slots<R, T>(), glm = 0;  // (of `kern`, for kspec_note_variant)
   if constexpr (R == 7 && sizeof(T) == 4 && PAR == 0) {
-    if (kspec_glds7()) kern = kspec_kernel<R, T, W, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR, 1>;
-    if (kspec_ns7() == 3) kern = kspec_kernel<R, T, W, 3, kspec_xmode<R, T>(), PAR>;
+    if (kspec_glds7()) {
+      kern = kspec_kernel<R, T, W, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR, 1>;
+      glm = 1;
+    }
+    if (kspec_ns7() == 3) {
+      kern = kspec_kernel<R, T, W, 3, kspec_xmode<R, T>(), PAR>;
+      ns = 3;
+      glm = 0;
+    }
     if (kspec_w8()) {
       constexpr int W8 = 8;
       auto k = kspec_kernel<R, T, W8, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR, 1>;
+      kspec_note_variant<R, T>(W8, kspec_slots<R, T>(), PAR, 1);
       const int nt = (a.lines + W8 - 1) / W8;
       dim3 grid(std::min(nt, resident_blocks(reinterpret_cast<const void*>(k), W8 * 64))), block(W8 * 64);
       hipLaunchKernelGGL(k, grid, block, 0, stream, t.tab, a);
@@ -1358,7 +1395,9 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
   }
   const int sp = kspec_split_env();
   if constexpr (kspec_split_default<R, T>()) {
+    if (sp == 1 && a.out6) kspec_split_ignored_note();
     if (sp == 1 && !a.out6) {  // (the output kernel writes the combine outputs)
+      kspec_note_variant<R, T>(W, kspec_slots<R, T>(), PAR, 0, 1, 1, kspec_out_lines<R, T>());
       auto k1 = kspec_kernel<R, T, W, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR, 0, 1>;
       const int nt1 = (a.lines + W - 1) / W;
       dim3 g1(std::min(nt1, resident_blocks(reinterpret_cast<const void*>(k1), W * 64))), b1(W * 64);
@@ -1371,6 +1410,7 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
       return;
     }
   }
+  kspec_note_variant<R, T>(W, ns, PAR, glm);
   // persistent grid: as many blocks as can be resident at once
   const int ntiles = (a.lines + W - 1) / W;
   dim3 grid(std::min(ntiles, resident_blocks(reinterpret_cast<const void*>(kern), W * 64))), block(W * 64);

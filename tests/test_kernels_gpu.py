@@ -316,6 +316,12 @@ for dtype, tol in ((torch.complex64, 5e-6), (torch.complex128, 1e-12)):
     e = np.linalg.norm(H.cpu().numpy() - Href) / np.linalg.norm(Href)
     assert e < tol, (dtype, e)
     assert abs(m.cpu().numpy()[0] - np.abs(u).max()) < 1e-4 * np.abs(u).max()
+# all four CFL maxima with a plane offset, the non-uniform 1 / dy, cx != cz and accumulation over two
+# calls (test_timestep_gpu.py::test_zphys_cfl_maxima, here on the register kernel)
+sys.path.insert(0, os.path.join(os.environ["CHANNEL_ROOT"], "tests"))
+from test_timestep_gpu import check_zstage_maxima
+for dtype in (torch.complex64, torch.complex128):
+    check_zstage_maxima(C, 16, 1024, dtype)
 print("ZREG_OK")
 """
 

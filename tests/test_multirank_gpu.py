@@ -147,6 +147,90 @@ def test_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mo
             assert not any(f.endswith(".turn") for f in os.listdir(d))
 
 
+def _worker_adaptive(rank, world, shm, outdir, nsteps, pr=1):
+    """No dt_fixed: every step's dt comes from the ranks' max-allreduced CFL maxima.  Stores the log of
+    every step, the statistics of prepare() and of the last step (step(True)) and the final state."""
+    import torch  # noqa: F401
+
+    from channel_gpu_amd import require_native
+    from channel_gpu_amd.utils.config import default_config
+
+    C = require_native()
+    cfg = default_config(**GRID, Re=400.0, precision="fp64", cfl=0.5, dt_max=0.05, ic="zero", stats_every=1,
+                         log_every=0, symmetry_every=0, decomposition="pencil" if pr > 1 else "slab", pr=pr)
+    s = C.Solver(cfg, rank, world, 0, shm.encode())
+    p = s.plan
+    phi, om, U = _global_state()
+    sl = slice(p.kx0, p.kx0 + p.nkx_loc)
+    sz = slice(p.kz0, p.kz0 + p.nkz_loc)
+    s.set_state(np.ascontiguousarray(phi[:, sl, sz]), np.ascontiguousarray(om[:, sl, sz]), U)
+    s.prepare()
+    st0 = np.asarray(s.stats())
+    logs = []
+    for i in range(nsteps):
+        s.step(i == nsteps - 1)
+        L = s.log()
+        logs.append([L.dt, L.umax, L.vmax, L.wmax, L.cflsum, L.time, L.dt_c, float(L.health)])
+    st1 = np.asarray(s.stats())
+    gphi, gom, gU = s.get_state()
+    np.savez(os.path.join(outdir, f"r{rank}.npz"), phi=gphi, om=gom, U=gU, logs=np.array(logs), st0=st0, st1=st1,
+             kx0=p.kx0, kz0=p.kz0)
+    del s
+
+
+@pytest.mark.parametrize("world,pr,chunk", [(2, 1, "0"), (3, 1, "4"), (4, 2, "4")])
+def test_multirank_adaptive_dt_and_stats_match_oracle(native, monkeypatch, world, pr, chunk):
+    """The ranks' dt, logged CFL maxima (max-allreduce over ranks whose slabs start at y0 > 0, split
+    into exchange chunks) and plane statistics (sum-allreduce; pr = 2: a pencil row with kz0 > 0,
+    whose kz = 0 weight must not apply) against the P = 1 oracle replayed with the ranks' dts; every
+    rank must log identical values.  Two steps, the second with step(True)."""
+    import refchecks as rc
+
+    monkeypatch.setenv("CHANNEL_YCHUNK", chunk)
+    nsteps = 2
+    shm = f"shm:chtestdt_{uuid.uuid4().hex[:12]}"
+    with tempfile.TemporaryDirectory() as d:
+        mp.start_processes(_worker_adaptive, args=(world, shm, d, nsteps, pr), nprocs=world, join=True,
+                           start_method="spawn")
+        parts = [dict(np.load(os.path.join(d, f"r{r}.npz"))) for r in range(world)]
+    logs = parts[0]["logs"]
+    for q in parts[1:]:
+        assert np.array_equal(q["logs"], logs), "ranks logged different dt / maxima / time"
+    assert pr == 1 or any(int(q["kz0"]) > 0 for q in parts)
+    o = ora.OracleSolver(**GRID, Re=400.0, cfl=0.5, dt_max=0.05)
+    phi, om, U = _global_state()
+    o.set_state(phi, om, U)
+    o.prepare()
+    rc.assert_stats_sensitive(o)
+    e0 = np.max([rc.stats_errors(q["st0"], o.plane_stats()) for q in parts], axis=0)  # (every rank holds the sum)
+    tsum = 0.0
+    for it in range(nsteps):
+        dt, umax, vmax, wmax, csum, time, dt_c, health = logs[it]
+        p = o.plan
+        u, v, w = ora.spec_to_phys_full(o.fields[:3], p)
+        # (precondition; chunk 0: a rank's slab is the chunk)
+        rc.assert_cfl_sensitive(u, v, w, o.inv_dy, 0, p.ax * p.Kx, p.az * p.Kz, chunk=int(chunk) or GRID["NY"] // world)
+        o.dt_fixed = dt
+        o.step()
+        err = np.abs(np.array([umax, vmax, wmax, csum]) - o.maxima) / o.maxima
+        dt_ref = min(0.5 / o.maxima[3], 0.05)
+        tsum += dt
+        print(f"P={world} step {it}: dt {dt:.10e} oracle {dt_ref:.10e}, maxima rel err {err}")
+        assert dt_ref < 0.05 and health == 0
+        assert (err[:3] < rc.TOL_MAX_F64).all() and err[3] < rc.TOL_SUM_F64, err
+        assert abs(dt - dt_ref) < rc.TOL_SUM_F64 * dt_ref and abs(dt_c - dt_ref) < rc.TOL_SUM_F64 * dt_ref
+        assert abs(time - tsum) <= 1e-14 * tsum
+    assert abs(logs[1][0] - logs[0][0]) >= 1e-4 * logs[0][0]  # (precondition: the step adapts)
+    rc.assert_stats_sensitive(o)
+    e1 = np.max([rc.stats_errors(q["st1"], o.plane_stats()) for q in parts], axis=0)
+    print(f"P={world} statistics rel err: prepare {e0}, step(True) {e1}")
+    assert max(e0) < rc.STATS_TOL_F64 and max(e1) < rc.STATS_TOL_F64
+    gphi, gom = _assemble(parts, "phi"), _assemble(parts, "om")
+    assert np.abs(gphi - o.phi).max() < 1e-9 * np.abs(o.phi).max()
+    assert np.abs(gom - o.om).max() < 1e-9 * np.abs(o.om).max()
+    assert np.abs(parts[0]["U"] - o.U).max() < 1e-11
+
+
 def _worker_big(rank, world, shm, outdir, grid, nsteps, pr=1):
     import torch  # noqa: F401
 

@@ -97,3 +97,35 @@ def test_parity_modes_differ_from_default_but_stay_close():
     v = ora._bsolve(ora.helm_matrix(o.ops, o.k2), o.ops.M @ o.lines(o.phi))
     dv = o.ops.D1 @ v
     assert np.abs(dv[[0, -1]]).max() < 1e-9 * max(1.0, np.abs(v).max())
+
+
+def test_forcing_parity_adds_constant_to_interior_rows():
+    """forcing = "parity" (COMPAT.md "mean forcing", meanUevol.c:201-221): the solved mean profile gets
+    half its flux defect on every interior row and nothing on the wall rows; the default adds the
+    implicit response to a uniform pressure gradient, which restores the flux exactly.  The two
+    differ, and only the default holds the flux."""
+    res = {}
+    for forcing in ("implicit", "parity"):
+        o = ora.OracleSolver(32, 33, 17, Re=400.0, dt_fixed=0.01, forcing=forcing)
+        phi, om = ora.random_state(o.plan, o.ops, seed=3, amp=0.3)
+        U0 = 0.7 * 1.8 * (1 - o.ops.y ** 2)  # flux 1.68: a defect for the forcing to act on
+        o.set_state(phi, om, U0)
+        o.prepare()
+        o.dt = 0.01
+        o.transforms(compute_dt=False)
+        o.substep(0)
+        res[forcing] = o
+    oi, op = res["implicit"], res["parity"]
+    assert np.array_equal(oi.mean_U1, op.mean_U1) and oi.mean_flux == op.mean_flux  # same solve before the forcing
+    # parity: U = U_solved + C on rows 1 .. N-2 with C = (Q - flux) / 2, walls as solved (no slip: 0)
+    add = op.U - (oi.U - oi.mean_C * oi.mean_U1)
+    C = (1.8 - op.mean_flux) / 2.0
+    assert abs(op.mean_C - C) < 1e-15 and abs(C) > 1e-3
+    assert np.abs(add[1:-1] - C).max() < 1e-13 and add[0] == 0.0 and add[-1] == 0.0
+    assert op.U[0] == 0.0 and op.U[-1] == 0.0
+    # the forcings differ, and only the implicit one restores the flux to round-off
+    # (both add about C in the core; they part in the wall layers of U1, here by 2.4e-4)
+    assert np.abs(op.U - oi.U).max() > 1e-5 * np.abs(oi.U).max()
+    assert abs(oi.ops.trap @ oi.U - 1.8) < 1e-12 and abs(op.ops.trap @ op.U - 1.8) > 1e-6
+    with pytest.raises(ValueError):
+        ora.OracleSolver(32, 33, 17, forcing="constant")

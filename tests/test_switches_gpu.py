@@ -1,7 +1,10 @@
 """Opt-in kernel variants behind environment switches, each checked in a fresh child process (the
 switches are read once per process): CHANNEL_ZFFT (z-stage row plans, incl. the paired-row H_z of
 ZFFT=4 on odd row counts) against NumPy, CHANNEL_KSPEC_W8 (K-SPEC at 8 lines, two waves per SIMD)
-against the fp64 oracle, CHANNEL_XSEGROWS=0 (per-element exchange-segment lookups of the P > 1 x
+against the fp64 oracle, the K-SPEC A/B variants CHANNEL_KSPEC_SPLIT (advance + output kernel, combine
+mode), CHANNEL_KSPEC_GLDS7, CHANNEL_KSPEC_NS7 (R = 7 fp32) and CHANNEL_KSPEC_VAR = w4 | ns2 | ns5 | ns7
+(R = 3) against the oracle in state and plane statistics, each asserting the kernel it launched
+(kspec_last_variant), CHANNEL_XSEGROWS=0 (per-element exchange-segment lookups of the P > 1 x
 kernels) bitwise against the single-rank fast path.  README "Environment switches" lists them."""
 import os
 import subprocess
@@ -91,6 +94,101 @@ def test_kspec_w8_matches_oracle():
     LDS staging) against the fp64 oracle at the one-wave kernel's fp32 tolerance
     (test_solver_gpu.py::test_gpu_matches_oracle_large_ny[fp32-385])."""
     _child(W8_SCRIPT, {"CHANNEL_KSPEC_W8": "1"}, "W8_OK")
+
+
+KSPEC_SWITCH_SCRIPT = r"""
+import os, sys
+import numpy as np
+sys.path.insert(0, os.environ["CHANNEL_ROOT"])
+sys.path.insert(0, os.path.join(os.environ["CHANNEL_ROOT"], "tests"))
+import refchecks as rc
+from channel_gpu_amd import require_native
+from channel_gpu_amd.reference import oracle as ora
+from channel_gpu_amd.utils.config import default_config
+C = require_native()
+NY, precision, variant = int(os.environ["SW_NY"]), os.environ["SW_PRECISION"], os.environ["SW_VARIANT"]
+NX, NZ, dt = 16, 9, 1e-4
+cfg = default_config(NX=NX, NY=NY, NZ=NZ, Re=400.0, precision=precision, dt_fixed=dt, stats_every=1, log_every=0,
+                     symmetry_every=0, ic="zero")
+s = C.Solver(cfg, 0, 1, 0, b"")
+o = ora.OracleSolver(NX, NY, NZ, Re=400.0, dt_fixed=dt)
+phi, om = ora.random_state(o.plan, o.ops, seed=5, amp=0.05)
+if precision == "fp32":
+    phi = phi.astype(np.complex64).astype(np.complex128)
+    om = om.astype(np.complex64).astype(np.complex128)
+U = 0.75 * 1.8 * (1 - o.ops.y ** 2)
+o.set_state(phi, om, U)
+s.set_state(phi, om, U)
+s.prepare()
+o.prepare()
+assert C.kspec_last_variant() == variant, C.kspec_last_variant()
+rc.assert_stats_sensitive(o)
+stol = rc.stats_tol(precision, NY)
+tol, tolU = (1e-9, 1e-11) if precision == "fp64" else (1e-4 * max(1.0, NY / 600), 1e-5)
+e = rc.stats_errors(s.stats(), o.plane_stats())
+print("STATS_ERR", precision, NY, variant, "prepare", e)
+assert max(e) < stol, ("prepare()", e)
+rel = lambda a, b: np.linalg.norm(a - b) / np.linalg.norm(b)
+for it in range(2):
+    o.step()
+    s.step(True)
+    assert C.kspec_last_variant() == variant, C.kspec_last_variant()
+    gphi, gom, gU = s.get_state()
+    es = rel(gphi, o.phi), rel(gom, o.om), rel(gU, o.U)
+    e = rc.stats_errors(s.stats(), o.plane_stats())
+    print("STATS_ERR", precision, NY, variant, "step", it, e, "state", es)
+    assert es[0] < tol and es[1] < tol and es[2] < tolU, (it, es)
+    assert max(e) < stol, ("step(True)", it, e)
+assert s.health() == 0
+print("KSPEC_SWITCH_OK")
+"""
+
+SPLIT_NOTE = "CHANNEL_KSPEC_SPLIT ignored"
+
+
+def _kspec_switch(env, NY, precision, variant, note=False):
+    env = dict(os.environ, CHANNEL_ROOT=ROOT, SW_NY=str(NY), SW_PRECISION=precision, SW_VARIANT=variant, **env)
+    r = subprocess.run([sys.executable, "-c", KSPEC_SWITCH_SCRIPT], env=env, capture_output=True, text=True, timeout=300)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0 and "KSPEC_SWITCH_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert (SPLIT_NOTE in r.stderr) == note, r.stderr[-2000:]
+    assert r.stderr.count(SPLIT_NOTE) <= 1  # (a one-time note)
+
+
+@pytest.mark.parametrize("NY,R", [(289, 5), (385, 7)])
+def test_kspec_split_matches_oracle(NY, R):
+    """CHANNEL_KSPEC_SPLIT=1 in the combine mode (CHANNEL_COMBINE=1), fp32: the advance kernel stops
+    after the phi / v stores and kspec_out_kernel forms D1 v, D1 omega and the statistics from the
+    stored fields with its own row map.  Two steps against the oracle: state at the fp32 tolerance of
+    test_gpu_matches_oracle_large_ny, prepare() and step(True) statistics at refchecks.stats_tol."""
+    _kspec_switch({"CHANNEL_KSPEC_SPLIT": "1", "CHANNEL_COMBINE": "1"}, NY, "fp32",
+                  f"kspec_kernel<{R}, float, 4, 2, 2, 0, 0, 1, 1> + kspec_out_kernel<{R}, float, 8, 2>")
+
+
+def test_kspec_split_ignored_in_six_output_mode():
+    """CHANNEL_KSPEC_SPLIT=1 without the combine mode (the one-rank default writes the six fields, which
+    the output kernel does not): the fused kernel runs, and says so once on stderr, so that an A/B
+    run cannot measure the wrong kernel silently."""
+    _kspec_switch({"CHANNEL_KSPEC_SPLIT": "1"}, 385, "fp32", "kspec_kernel<7, float, 4, 2, 2, 0, 0, 0, 1>", note=True)
+
+
+@pytest.mark.parametrize("env,variant", [
+    ({"CHANNEL_KSPEC_GLDS7": "1"}, "kspec_kernel<7, float, 4, 2, 2, 0, 1, 0, 1>"),
+    ({"CHANNEL_KSPEC_NS7": "3"}, "kspec_kernel<7, float, 4, 3, 2, 0, 0, 0, 1>"),
+], ids=["glds7", "ns7=3"])
+def test_kspec_r7_variants_match_oracle(env, variant):
+    """The R = 7 fp32 A/B variants at NY = 385: async LDS staging in place of the two register slots
+    (CHANNEL_KSPEC_GLDS7=1), three register prefetch slots (CHANNEL_KSPEC_NS7=3)."""
+    _kspec_switch(env, 385, "fp32", variant)
+
+
+@pytest.mark.parametrize("var,precision,W,NS", [("w4", "fp64", 4, 1), ("ns2", "fp64", 8, 2), ("ns5", "fp64", 8, 5),
+                                                ("ns7", "fp64", 8, 7), ("w4", "fp32", 4, 1)])
+def test_kspec_r3_variants_match_oracle(var, precision, W, NS):
+    """CHANNEL_KSPEC_VAR at NY = 129 (R = 3): 4 lines per workgroup with one slot (w4), or 8 lines
+    with 2 / 5 / 7 register prefetch slots."""
+    T = "double" if precision == "fp64" else "float"
+    _kspec_switch({"CHANNEL_KSPEC_VAR": var}, 129, precision, f"kspec_kernel<3, {T}, {W}, {NS}, 2, 0, 0, 0, 1>")
 
 
 SEGROWS_SCRIPT = r"""
