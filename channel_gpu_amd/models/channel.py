@@ -110,10 +110,25 @@ class ChannelFlow:
     def mean_profile(self) -> np.ndarray:
         return np.asarray(self.solver.mean_profile())
 
+    # ---- physical space (one rank) --------------------------------------------------------------
+    def physical_fields(self, planes=None, fields=("u", "v", "w")) -> dict:
+        """Physical-space planes of the current state: ``{name: ndarray (nplanes, NX, Nzp)}`` for
+        ``fields`` out of u, v, w, wx, wy, wz at the y indices ``planes`` (default: every plane).
+        The step keeps no physical field in memory; this runs the export stage on request."""
+        if planes is None:
+            planes = range(self.cfg.NY)
+        return self.solver.physical_fields([int(j) for j in planes], [str(f) for f in fields])
+
+    def plane_moments(self) -> np.ndarray:
+        """Plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4 with
+        u' = u - U(y): ``ndarray (11, NY)`` (``statistics.MOMENT_ROWS``)."""
+        return np.asarray(self.solver.plane_moments())
+
     # ---- time-averaged statistics -------------------------------------------------------------
-    def sample_statistics(self, nsteps: int, every: int = 10):
+    def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
-        calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``."""
+        calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
+        ``moments``: also the third and fourth central moments (skewness / flatness profiles)."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -124,6 +139,8 @@ class ChannelFlow:
                 L = self.solver.log()
                 self.statistics.add(np.asarray(self.solver.mean_profile()), np.asarray(self.solver.stats()), L.utau_lo,
                                     L.utau_hi, L.time)
+                if moments:
+                    self.statistics.add_moments(self.plane_moments())
         return self.statistics
 
     def grid_points(self) -> int:

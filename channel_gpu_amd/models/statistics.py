@@ -7,13 +7,18 @@ reduces on the device — U(y), the plane mean squares <u'u'>, <v'v'>, <w'w'>, <
 plane sums, all ranks reduced) and the wall friction velocities — and produces the standard
 wall-unit profiles folded over the two channel halves: U+(y+), u'+, v'+, w'+ r.m.s., -<u'v'>+,
 plus the scalar checks of a statistically steady Re_tau~180 channel (Re_tau, U+_c, the u'+ peak
-and its y+).
+and its y+).  Optionally it also averages the one-point central moments of the physical-space
+export (``Solver.plane_moments``) into skewness and flatness profiles of u, v, w.
 """
 from __future__ import annotations
 
 import json
 
 import numpy as np
+
+
+# rows of Solver.plane_moments()
+MOMENT_ROWS = ("u", "uu", "vv", "ww", "uv", "uuu", "vvv", "www", "uuuu", "vvvv", "wwww")
 
 
 class TurbulenceStatistics:
@@ -30,6 +35,14 @@ class TurbulenceStatistics:
         self.tau = 0.0              # mean wall shear velocity squared (both walls)
         self.t0 = None
         self.t1 = None
+        self.nm = 0
+        self.mom = np.zeros((len(MOMENT_ROWS), n))
+
+    def add_moments(self, m):
+        """One sample of the raw central moments [11, NY] (``MOMENT_ROWS``); the moments are
+        averaged, the skewness and flatness ratios formed from the averages."""
+        self.mom += np.asarray(m, float).reshape(len(MOMENT_ROWS), self.y.size)
+        self.nm += 1
 
     def add(self, U, stats, utau_lo: float, utau_hi: float, t: float | None = None):
         """One sample: U(y) [NY], stats [4*NY] (uu, vv, ww, uv plane means), u_tau at both walls."""
@@ -60,7 +73,7 @@ class TurbulenceStatistics:
         hi = n - 1 - lo  # mirror points
         fold = lambda a, s=1.0: 0.5 * (a[lo] + s * a[hi])  # noqa: E731
         yplus = (1.0 + self.y[lo]) * ut / self.nu
-        return {
+        out = {
             "y": self.y[lo],
             "yplus": yplus,
             "Uplus": fold(U) / ut,
@@ -70,6 +83,16 @@ class TurbulenceStatistics:
             # <u'v'> is antisymmetric about the centreline
             "uvplus": -fold(ms[3], -1.0) / ut ** 2,
         }
+        if self.nm:
+            mom = self.mom / self.nm
+            for q, (r2, r3, r4) in zip("uvw", ((1, 5, 8), (2, 6, 9), (3, 7, 10))):
+                m2 = mom[r2]
+                ok = m2 > 0  # (the walls: 0)
+                d = np.where(ok, m2, 1.0)
+                # v-skewness is antisymmetric about the centreline (v -> -v under the reflection)
+                out["skew_" + q] = fold(np.where(ok, mom[r3] / d ** 1.5, 0.0), -1.0 if q == "v" else 1.0)
+                out["flat_" + q] = fold(np.where(ok, mom[r4] / d ** 2, 0.0))
+        return out
 
     def summary(self) -> dict:
         p = self.profiles()
@@ -97,8 +120,14 @@ class TurbulenceStatistics:
     def write(self, path: str):
         """Profiles as whitespace columns (y, y+, U+, u'+, v'+, w'+, -u'v'+) with a JSON summary header."""
         p = self.profiles()
-        cols = np.column_stack([p["y"], p["yplus"], p["Uplus"], p["urms"], p["vrms"], p["wrms"], p["uvplus"]])
+        cols = [p["y"], p["yplus"], p["Uplus"], p["urms"], p["vrms"], p["wrms"], p["uvplus"]]
+        names = "y yplus Uplus urms_plus vrms_plus wrms_plus minus_uv_plus"
+        if self.nm:
+            extra = ["skew_u", "skew_v", "skew_w", "flat_u", "flat_v", "flat_w"]
+            cols += [p[k] for k in extra]
+            names += " " + " ".join(extra)
+        cols = np.column_stack(cols)
         with open(path, "w") as f:
             f.write("# " + json.dumps(self.summary()) + "\n")
-            f.write("# y yplus Uplus urms_plus vrms_plus wrms_plus minus_uv_plus\n")
+            f.write("# " + names + "\n")
             np.savetxt(f, cols, fmt="%.6e")

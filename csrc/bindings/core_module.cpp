@@ -72,7 +72,8 @@ PYBIND11_MODULE(_core, m) {
       RW(LX) RW(LZ) RW(stretch) RW(nsteps) RW(t_end) RW(cfl) RW(dt_fixed) RW(dt_max) RW(cfl_mode) RW(stats_every)
       RW(symmetry_every) RW(checkpoint_every) RW(log_every) RW(precision) RW(decomposition) RW(pr) RW(pc) RW(seed)
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
-      RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json);
+      RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
+      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -245,7 +246,39 @@ PYBIND11_MODULE(_core, m) {
              d["map"] = arr(sp.map, {3, p.nkx, p.nkz});
              return d;
            },
-           "energy spectra of u, v, w of the current state at cfg.spectra_planes (global)");
+           "energy spectra of u, v, w of the current state at cfg.spectra_planes (global)")
+      .def("physical_fields",
+           [](Solver& s, const std::vector<int>& planes, const std::vector<std::string>& names) {
+             // the arrays view the result in place (a capsule owns it): no second host copy
+             auto pf = std::make_unique<Solver::PhysFields>();
+             {
+               py::gil_scoped_release r;
+               *pf = s.physical_fields(planes, names);
+             }
+             Solver::PhysFields* raw = pf.release();
+             py::capsule owner(raw, [](void* q) { delete static_cast<Solver::PhysFields*>(q); });
+             const py::ssize_t np = static_cast<py::ssize_t>(raw->planes.size());
+             const size_t per = static_cast<size_t>(np) * raw->NX * raw->Nzp;
+             py::dict d;
+             for (size_t f = 0; f < raw->names.size(); ++f)
+               d[py::str(raw->names[f])] = py::array_t<double>({np, static_cast<py::ssize_t>(raw->NX), static_cast<py::ssize_t>(raw->Nzp)},
+                                                                raw->data.data() + f * per, owner);
+             return d;
+           },
+           py::arg("planes"), py::arg("names"),
+           "physical-space planes of the current state: name -> (nplanes, NX, Nzp) float64 (one rank)")
+      .def("plane_moments",
+           [](Solver& s) {
+             std::vector<double> m;
+             {
+               py::gil_scoped_release r;
+               m = s.plane_moments();
+             }
+             py::array_t<double> a({static_cast<py::ssize_t>(kMomRows), static_cast<py::ssize_t>(s.plan().NY)});
+             std::copy(m.begin(), m.end(), a.mutable_data());
+             return a;
+           },
+           "plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4: (11, NY) (one rank)");
 
   py::class_<ProcInfo>(m, "ProcInfo")
       .def(py::init<>())

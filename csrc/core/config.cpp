@@ -222,6 +222,10 @@ Config Config::from_tree(const ConfigTree& t) {
   c.spectra_every = static_cast<int>(t.get_int(pick(t, "spectra_every"), c.spectra_every));
   c.spectra_planes = t.get_string(pick(t, "spectra_planes"), c.spectra_planes);
   c.log_json = t.get_string(pick(t, "log_json"), c.log_json);
+  c.fields_every = static_cast<int>(t.get_int(pick(t, "fields_every"), c.fields_every));
+  c.fields_planes = t.get_string(pick(t, "fields_planes"), c.fields_planes);
+  c.fields = t.get_string(pick(t, "fields"), c.fields);
+  c.moments_every = static_cast<int>(t.get_int(pick(t, "moments_every"), c.moments_every));
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -240,21 +244,50 @@ Config Config::from_file(const std::string& path, const std::vector<std::string>
   return from_tree(t);
 }
 
-std::vector<int> Config::spectra_plane_list() const {
-  std::vector<int> out;
+namespace {
+std::vector<std::string> split_list(const std::string& s) {
+  std::vector<std::string> out;
   std::string tok;
-  std::istringstream is(spectra_planes);
+  std::istringstream is(s);
   while (std::getline(is, tok, ',')) {
     tok.erase(0, tok.find_first_not_of(" \t"));
     tok.erase(tok.find_last_not_of(" \t") + 1);
-    if (tok.empty()) continue;
+    if (!tok.empty()) out.push_back(tok);
+  }
+  return out;
+}
+std::vector<int> int_list(const std::string& s, const char* key) {
+  std::vector<int> out;
+  for (const std::string& tok : split_list(s)) {
     char* end = nullptr;
     const long v = std::strtol(tok.c_str(), &end, 10);
-    CH_CHECK(end && *end == '\0', "spectra_planes: '" << tok << "' is not an integer");
+    CH_CHECK(end && *end == '\0', key << ": '" << tok << "' is not an integer");
     out.push_back(static_cast<int>(v));
   }
+  return out;
+}
+}  // namespace
+
+std::vector<int> Config::spectra_plane_list() const {
+  std::vector<int> out = int_list(spectra_planes, "spectra_planes");
   if (out.empty()) out.push_back(NY / 2);
   return out;
+}
+
+std::vector<int> Config::fields_plane_list() const {
+  std::vector<int> out = int_list(fields_planes, "fields_planes");
+  if (out.empty())
+    for (int j = 0; j < NY; ++j) out.push_back(j);
+  return out;
+}
+
+std::vector<std::string> Config::fields_list() const { return split_list(fields); }
+
+int phys_field_index(const std::string& name) {
+  static const char* kNames[6] = {"u", "v", "w", "wx", "wy", "wz"};
+  for (int f = 0; f < 6; ++f)
+    if (name == kNames[f]) return f;
+  return -1;
 }
 
 // transform lengths with kernels (kernels/fft.hip CH_DISPATCH_N): 2^k in [16, 2048], and m*2^k
@@ -288,13 +321,18 @@ void Config::validate() const {
   CH_CHECK(ic == "random" || ic == "laminar" || ic == "file" || ic == "os_mode" || ic == "zero",
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
-               spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1,
+               spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
   CH_CHECK(rollback_cfl_factor > 0 && rollback_cfl_factor <= 1, "rollback_cfl_factor must be in (0, 1]");
   CH_CHECK(max_rollbacks >= 0, "max_rollbacks must be >= 0");
   for (int j : spectra_plane_list())
     CH_CHECK(j >= 0 && j < NY, "spectra_planes: y index " << j << " outside [0, NY)");
+  for (int j : fields_plane_list())
+    CH_CHECK(j >= 0 && j < NY, "fields_planes: y index " << j << " outside [0, NY)");
+  CH_CHECK(!fields_list().empty(), "fields must name at least one of u, v, w, wx, wy, wz");
+  for (const std::string& f : fields_list())
+    CH_CHECK(phys_field_index(f) >= 0, "fields: unknown field '" << f << "' (u, v, w, wx, wy, wz)");
 }
 
 std::string Config::to_string() const {
@@ -321,6 +359,8 @@ std::string Config::to_string() const {
   o << "  snapshot_every = " << snapshot_every << ";\n  max_rollbacks = " << max_rollbacks << ";\n";
   o << "  rollback_cfl_factor = " << rollback_cfl_factor << ";\n  spectra_every = " << spectra_every << ";\n";
   o << "  spectra_planes = \"" << spectra_planes << "\";\n  log_json = \"" << log_json << "\";\n";
+  o << "  fields_every = " << fields_every << ";\n  fields_planes = \"" << fields_planes << "\";\n";
+  o << "  fields = \"" << fields << "\";\n  moments_every = " << moments_every << ";\n";
   o << "};\n";
   return o.str();
 }

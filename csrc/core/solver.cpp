@@ -164,6 +164,8 @@ Solver::Solver(const Config& cfg, int rank, int nranks, int device, const std::s
     kspec_geometry(cfg_.NY, fp64_, R, H);
     ytab_.upload(grid_, R, s_comp_, H);
   }
+  CH_CHECK(!comm_ || (cfg_.fields_every == 0 && cfg_.moments_every == 0),
+           "fields_every / moments_every: the physical-space export is single-rank (one rank without a communicator)");
   tw_x_.build(plan_.NX, fp64_);
   tw_z_.build(plan_.Nzp, fp64_);
   choose_layout();
@@ -449,9 +451,11 @@ void Solver::free_all() {
   if (h_tdt_) (void)hipHostFree(h_tdt_);
   h_tdt_ = nullptr;
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
-                  static_cast<void*>(d_rowtab_)})
+                  static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_)})
     if (p) (void)hipFree(p);
-  state_ = out_ = phys_ = xbuf_ = zbuf_ = dscal_ = snap_ = d_spec_ = d_sym_ = nullptr;
+  state_ = out_ = phys_ = xbuf_ = zbuf_ = dscal_ = snap_ = d_spec_ = d_sym_ = d_real_ = nullptr;
+  d_mom_ = nullptr;
+  real_n_ = 0;
   d_rowtab_ = nullptr;
   d_y_ = nullptr;
 }
@@ -851,7 +855,7 @@ std::vector<double> Solver::kspec_profile() {
   return std::vector<double>(h.begin(), h.end());
 }
 
-void Solver::transforms(int n, bool /*stats*/) {
+XArgs Solver::x_args() const {
   const Plan& p = plan_;
   XArgs xa;
   xa.NX = p.NX;
@@ -869,6 +873,46 @@ void Solver::transforms(int n, bool /*stats*/) {
   xa.kz_glob0 = p.kz0;
   xa.lds_poison = lds_poison_enabled() ? 1 : 0;
   xa.nt = xnt_;
+  return xa;
+}
+
+// one rank: the spectral fields are blocked by 8 kz lines (kzb_, spec_index); the x transforms
+// address rows spec_y0 .. of the full fields
+XSrc Solver::x_src_local(XArgs& xa) const {
+  const Plan& p = plan_;
+  xa.kzb = kzb_;
+  xa.nkzs = nkzs_;
+  xa.spec_y0 = 0;
+  XSrc src;
+  src.base = out_;
+  src.nsrc = 1;
+  src.kx_start[0] = 0;
+  src.kx_start[1] = p.nkx;
+  if (combine_)
+    for (int j = 0; j < kCmbIn; ++j) src.fld[j] = in_field(j);
+  xa.nfields = 6;
+  xa.field_stride_spec = static_cast<long long>(spec_);
+  return src;
+}
+
+// planes [y0, y0 + ny) of the one-rank source: rows of the blocked fields, or the plain fields
+// offset to the first plane
+void Solver::x_chunk(const XArgs& xa, const XSrc& src, int y0, int ny, XArgs& xc, XSrc& sc) const {
+  const Plan& p = plan_;
+  const size_t so = kzb_ ? 0 : static_cast<size_t>(y0) * p.nkx * p.nkz * esz_;
+  xc = xa;
+  xc.ny = ny;
+  if (kzb_) xc.spec_y0 = y0;
+  sc = src;
+  sc.base = static_cast<char*>(out_) + so;
+  if (combine_)
+    for (int j = 0; j < kCmbIn; ++j) sc.fld[j] = static_cast<const char*>(src.fld[j]) + so;
+  xc.nfields = 6;
+}
+
+void Solver::transforms(int n, bool /*stats*/) {
+  const Plan& p = plan_;
+  XArgs xa = x_args();
   ZArgs za;
   za.lds_poison = xa.lds_poison;
   za.NX = p.NX;
@@ -901,20 +945,7 @@ void Solver::transforms(int n, bool /*stats*/) {
   da.dy_uniform = 2.0 / (p.NY - 1);
 
   if (!comm_) {
-    // one rank: the spectral fields are blocked by 8 kz lines (kzb_, spec_index); the x transforms
-    // address rows spec_y0 .. of the full fields
-    xa.kzb = kzb_;
-    xa.nkzs = nkzs_;
-    xa.spec_y0 = 0;
-    XSrc src;
-    src.base = out_;
-    src.nsrc = 1;
-    src.kx_start[0] = 0;
-    src.kx_start[1] = p.nkx;
-    if (combine_)
-      for (int j = 0; j < kCmbIn; ++j) src.fld[j] = in_field(j);
-    xa.nfields = 6;
-    xa.field_stride_spec = static_cast<long long>(spec_);
+    XSrc src = x_src_local(xa);
     XDst dst;
     dst.base = out_;
     dst.ndst = 1;
@@ -942,14 +973,9 @@ void Solver::transforms(int n, bool /*stats*/) {
         hipStream_t cs = streams[ci % nst];
         const size_t so = kzb_ ? 0 : static_cast<size_t>(y0) * p.nkx * p.nkz * esz_;
         char* ph = static_cast<char*>(phys_) + static_cast<size_t>(y0) * p.NX * p.nkz * esz_;
-        XArgs xc = xa;
-        xc.ny = ny;
-        if (kzb_) xc.spec_y0 = y0;
-        XSrc sc = src;
-        sc.base = static_cast<char*>(out_) + so;
-        if (combine_)
-          for (int j = 0; j < kCmbIn; ++j) sc.fld[j] = static_cast<const char*>(src.fld[j]) + so;
-        xc.nfields = 6;
+        XArgs xc;
+        XSrc sc;
+        x_chunk(xa, src, y0, ny, xc, sc);
         ev(1, false, cs);
         xfft_backward(xc, sc, ph, tw_x_, fp64_, cs);
         ev(1, true, cs);
@@ -2132,6 +2158,8 @@ void Solver::run(long nsteps, bool verbose) {
       }
     }
     if (pe > 0 && nstep_ % pe == 0) write_spectra_files(spectra());
+    if (cfg_.fields_every > 0 && nstep_ % cfg_.fields_every == 0) write_field_files();
+    if (cfg_.moments_every > 0 && nstep_ % cfg_.moments_every == 0) write_moment_files(plane_moments());
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();
       prepare();
@@ -2334,6 +2362,225 @@ void Solver::write_spectra_files(const Spectra& sp) {
       for (int k = 0; k < p.nkz; ++k) fz << " " << sp.ekz[(static_cast<size_t>(q) * np + pl) * p.nkz + k];
       fz << "\n";
     }
+}
+
+// ---- physical-space export ------------------------------------------------------------------------
+// Between steps out_ (and the state) hold K-SPEC's outputs of the current state (as spectra()
+// relies on) and phys_ is scratch; everything goes on the compute stream behind whatever is queued
+// and touches nothing the next step reads, so the step graphs stay valid.
+// The x-backward addresses any plane range of the fields: rows spec_y0 + y through spec_row_off in
+// the blocked layout, planes past ny clamped at the loads and masked at the stores (also in the
+// plane tiles of the wide kernels), so a run of planes is transformed as it is requested.
+void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
+                           const std::function<void(int, int, const void*)>& sink) {
+  CH_CHECK(!comm_, "physical-space export is single-rank: it needs a solver without a communicator");
+  const Plan& p = plan_;
+  if (!prepared_) prepare();
+  const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
+  const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
+  const size_t plane = static_cast<size_t>(p.NX) * p.Nzp;
+  int nslots = 0;
+  for (int f = 0; f < 6; ++f) nslots += (out_mask >> f) & 1u;
+  if (nslots) {
+    const size_t need = static_cast<size_t>(nslots) * cap * plane * tsz;
+    if (real_n_ < need) {
+      HIP_CHECK(hipStreamSynchronize(s_comp_));
+      if (d_real_) HIP_CHECK(hipFree(d_real_));
+      d_real_ = nullptr;
+      real_n_ = 0;
+      HIP_CHECK(hipMalloc(&d_real_, need));
+      real_n_ = need;
+    }
+  }
+  XArgs xa = x_args();
+  const XSrc src = x_src_local(xa);
+  std::vector<char> host;
+  for (size_t i = 0; i < ys.size();) {
+    size_t j = i + 1;
+    while (j < ys.size() && ys[j] == ys[j - 1] + 1 && static_cast<int>(j - i) < cap) ++j;
+    const int y0 = ys[i], ny = static_cast<int>(j - i);
+    i = j;
+    XArgs xc;
+    XSrc sc;
+    x_chunk(xa, src, y0, ny, xc, sc);
+    if (!combine_) xc.nfields = nf;  // (the combine mode forms all six)
+    xfft_backward(xc, sc, phys_, tw_x_, fp64_, s_comp_);
+    ZRealArgs za;
+    za.NX = p.NX;
+    za.Nzp = p.Nzp;
+    za.nkz = p.nkz;
+    za.ny = ny;
+    za.y0 = y0;
+    za.nfields = nf;
+    za.field_stride = static_cast<long long>(physn_);
+    za.out = nslots ? d_real_ : nullptr;
+    za.out_mask = out_mask;
+    za.out_field_stride = static_cast<long long>(ny * plane);
+    za.moments = d_mom;
+    za.U = d_mean_;
+    za.NY = p.NY;
+    zreal(za, phys_, tw_z_, fp64_, s_comp_);
+    if (nslots) {
+      host.resize(static_cast<size_t>(nslots) * ny * plane * tsz);
+      HIP_CHECK(hipMemcpyAsync(host.data(), d_real_, host.size(), hipMemcpyDeviceToHost, s_comp_));
+      HIP_CHECK(hipStreamSynchronize(s_comp_));
+      sink(y0, ny, host.data());
+    }
+  }
+}
+
+Solver::PhysFields Solver::physical_fields(const std::vector<int>& planes, const std::vector<std::string>& names) {
+  CH_CHECK(!comm_, "physical_fields: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  CH_CHECK(!names.empty() && !planes.empty(), "physical_fields: no fields or no planes requested");
+  std::vector<int> fidx;
+  unsigned mask = 0;
+  int nf = 0;
+  for (const std::string& nm : names) {
+    const int f = phys_field_index(nm);
+    CH_CHECK(f >= 0, "physical_fields: unknown field '" << nm << "' (u, v, w, wx, wy, wz)");
+    fidx.push_back(f);
+    mask |= 1u << f;
+    nf = std::max(nf, f + 1);
+  }
+  for (int y : planes) CH_CHECK(y >= 0 && y < p.NY, "physical_fields: plane " << y << " outside [0, NY)");
+  std::vector<int> ys = planes;
+  std::sort(ys.begin(), ys.end());
+  ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
+  PhysFields out;
+  out.planes = planes;
+  out.names = names;
+  out.NX = p.NX;
+  out.Nzp = p.Nzp;
+  const size_t plane = static_cast<size_t>(p.NX) * p.Nzp, np = planes.size();
+  out.data.resize(names.size() * np * plane);
+  // positions of each plane in the request, slot of each field among the exported ones
+  std::vector<std::vector<size_t>> pos(p.NY);
+  for (size_t i = 0; i < np; ++i) pos[planes[i]].push_back(i);
+  int slot_of[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0, sl = 0; f < 6; ++f)
+    if ((mask >> f) & 1u) slot_of[f] = sl++;
+  export_planes(ys, nf, mask, nullptr, [&](int y0, int ny, const void* h) {
+    for (size_t k = 0; k < names.size(); ++k)
+      for (int y = 0; y < ny; ++y) {
+        const size_t so = (static_cast<size_t>(slot_of[fidx[k]]) * ny + y) * plane;
+        for (size_t i : pos[y0 + y]) {
+          double* d = out.data.data() + (k * np + i) * plane;
+          if (fp64_) std::copy(static_cast<const double*>(h) + so, static_cast<const double*>(h) + so + plane, d);
+          else std::copy(static_cast<const float*>(h) + so, static_cast<const float*>(h) + so + plane, d);
+        }
+      }
+  });
+  return out;
+}
+
+std::vector<double> Solver::plane_moments() {
+  CH_CHECK(!comm_, "plane_moments: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const size_t n = static_cast<size_t>(kMomRows) * p.NY;
+  if (!d_mom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_mom_), n * sizeof(double)));
+  if (!prepared_) prepare();
+  HIP_CHECK(hipMemsetAsync(d_mom_, 0, n * sizeof(double), s_comp_));
+  std::vector<int> ys(p.NY);
+  for (int j = 0; j < p.NY; ++j) ys[j] = j;
+  export_planes(ys, 3, 0u, d_mom_, nullptr);
+  std::vector<double> m(n);
+  HIP_CHECK(hipMemcpyAsync(m.data(), d_mom_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  return m;
+}
+
+// One NumPy v1.0 file per field, <path>FIELD_<name>_<step>.npy of shape (nplanes, NX, Nzp) in the
+// storage precision, and a sidecar <path>FIELDS_<step>.json
+void Solver::write_field_files() {
+  const Plan& p = plan_;
+  const std::vector<int> planes = cfg_.fields_plane_list();
+  const std::vector<std::string> names = cfg_.fields_list();
+  std::vector<int> ys = planes;
+  std::sort(ys.begin(), ys.end());
+  ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
+  unsigned mask = 0;
+  int nf = 0;
+  for (const std::string& nm : names) {
+    const int f = phys_field_index(nm);
+    mask |= 1u << f;
+    nf = std::max(nf, f + 1);
+  }
+  int slot_of[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0, sl = 0; f < 6; ++f)
+    if ((mask >> f) & 1u) slot_of[f] = sl++;
+  char step[16];
+  std::snprintf(step, sizeof(step), "%08ld", nstep_);
+  const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
+  const size_t plane = static_cast<size_t>(p.NX) * p.Nzp;
+  // header: magic, version 1.0, little-endian length, dict padded with spaces to a multiple of 64
+  // bytes in all, newline-terminated
+  std::string dict = std::string("{'descr': '") + (fp64_ ? "<f8" : "<f4") + "', 'fortran_order': False, 'shape': (" +
+                     std::to_string(planes.size()) + ", " + std::to_string(p.NX) + ", " + std::to_string(p.Nzp) + "), }";
+  const size_t hlen = (10 + dict.size() + 1 + 63) / 64 * 64 - 10;
+  dict.resize(hlen - 1, ' ');
+  dict.push_back('\n');
+  std::vector<std::ofstream> files;
+  for (const std::string& nm : names) {
+    files.emplace_back(cfg_.path + "FIELD_" + nm + "_" + step + ".npy", std::ios::binary | std::ios::trunc);
+    std::ofstream& f = files.back();
+    CH_CHECK(f.good(), "cannot open field file for '" << nm << "' under '" << cfg_.path << "'");
+    const char magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
+    f.write(magic, 8);
+    const unsigned char len[2] = {static_cast<unsigned char>(hlen & 0xff), static_cast<unsigned char>(hlen >> 8)};
+    f.write(reinterpret_cast<const char*>(len), 2);
+    f.write(dict.data(), static_cast<std::streamsize>(dict.size()));
+  }
+  const std::streamoff data0 = static_cast<std::streamoff>(10 + hlen);
+  std::vector<std::vector<size_t>> pos(p.NY);
+  for (size_t i = 0; i < planes.size(); ++i) pos[planes[i]].push_back(i);
+  export_planes(ys, nf, mask, nullptr, [&](int y0, int ny, const void* h) {
+    for (size_t k = 0; k < names.size(); ++k)
+      for (int y = 0; y < ny; ++y) {
+        const size_t so = (static_cast<size_t>(slot_of[phys_field_index(names[k])]) * ny + y) * plane * tsz;
+        for (size_t i : pos[y0 + y]) {
+          files[k].seekp(data0 + static_cast<std::streamoff>(i * plane * tsz));
+          files[k].write(static_cast<const char*>(h) + so, static_cast<std::streamsize>(plane * tsz));
+        }
+      }
+  });
+  for (size_t k = 0; k < names.size(); ++k) {
+    files[k].close();
+    CH_CHECK(!files[k].fail(), "writing the field file of '" << names[k] << "' failed");
+  }
+  double hv[2];
+  HIP_CHECK(hipMemcpy(hv, d_dt_, sizeof(hv), hipMemcpyDeviceToHost));
+  std::ofstream js(cfg_.path + "FIELDS_" + step + ".json");
+  js.precision(17);
+  js << "{\"step\": " << nstep_ << ", \"time\": " << hv[1] << ", \"planes\": [";
+  for (size_t i = 0; i < planes.size(); ++i) js << (i ? ", " : "") << planes[i];
+  js << "], \"y\": [";
+  for (size_t i = 0; i < planes.size(); ++i) js << (i ? ", " : "") << grid_.y[planes[i]];
+  js << "], \"fields\": [";
+  for (size_t k = 0; k < names.size(); ++k) js << (k ? ", " : "") << "\"" << names[k] << "\"";
+  js << "], \"NX\": " << p.NX << ", \"Nzp\": " << p.Nzp << ", \"LX\": " << cfg_.LX << ", \"LZ\": " << cfg_.LZ << "}\n";
+}
+
+// skewness m3 / m2^1.5 and flatness m4 / m2^2 of u, v, w per plane (0 where m2 = 0: the walls), one
+// line of NY values per call, as write_stats_files
+void Solver::write_moment_files(const std::vector<double>& m) {
+  const int N = plan_.NY;
+  auto app = [&](const char* name) { return std::ofstream(cfg_.path + name, std::ios::app); };
+  const char* sk[3] = {"USKEW.dat", "VSKEW.dat", "WSKEW.dat"};
+  const char* fl[3] = {"UFLAT.dat", "VFLAT.dat", "WFLAT.dat"};
+  const int r2[3] = {1, 2, 3}, r3[3] = {5, 6, 7}, r4[3] = {8, 9, 10};
+  for (int q = 0; q < 3; ++q) {
+    auto fs = app(sk[q]);
+    auto ff = app(fl[q]);
+    for (int j = 0; j < N; ++j) {
+      const double m2 = m[r2[q] * N + j];
+      const double d3 = m2 > 0 ? m2 * std::sqrt(m2) : 0.0, d4 = m2 * m2;  // (either may underflow to 0)
+      fs << " " << std::fixed << (d3 > 0 ? m[r3[q] * N + j] / d3 : 0.0);
+      ff << " " << std::fixed << (d4 > 0 ? m[r4[q] * N + j] / d4 : 0.0);
+    }
+    fs << " \n";
+    ff << " \n";
+  }
 }
 
 void Solver::write_json(const StepLog& L, double ms_per_step) {

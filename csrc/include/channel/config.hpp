@@ -85,6 +85,11 @@ struct Config {
   int spectra_every = 0;               // 0 = off; 1-D kx/kz energy spectra + 2-D map (statistics.cu:245-326)
   std::string spectra_planes = "";     // comma-separated y indices ("" = NY/2)
   std::string log_json = "";           // JSON-lines run log path ("" = off)
+  // Physical-space export (one rank; the step itself keeps no physical field in memory).
+  int fields_every = 0;                // 0 = off; FIELD_<name>_<step>.npy planes + FIELDS_<step>.json
+  std::string fields_planes = "";      // comma-separated y indices ("" = every plane)
+  std::string fields = "u,v,w";        // of u, v, w, wx, wy, wz
+  int moments_every = 0;               // 0 = off; skewness / flatness profiles of u, v, w (*SKEW.dat, *FLAT.dat)
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});
@@ -94,10 +99,14 @@ struct Config {
   int nzp() const { return 2 * NZ - 2; }
   bool fp64() const { return precision == "fp64"; }
   std::vector<int> spectra_plane_list() const;   // parsed spectra_planes (default {NY/2})
+  std::vector<int> fields_plane_list() const;    // parsed fields_planes (default: 0 .. NY-1)
+  std::vector<std::string> fields_list() const;  // parsed fields
 };
 
 // FFT lengths the transform kernels are instantiated for: 2^k (16..2048) and 3, 5, 7, 9, 11, 13, 15 x 2^k
 // (2^k >= 16, at most 2048 points)
 bool fft_length_supported(int n);
+// index of a physical-stage field name (u v w wx wy wz) or -1
+int phys_field_index(const std::string& name);
 
 }  // namespace channel

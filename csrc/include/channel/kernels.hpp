@@ -244,6 +244,28 @@ struct ZArgs {
 // -> truncated H_x,H_y,H_z written in place over fields 0..2.
 void zphys(const ZArgs& a, void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
 
+// export stage (on request, outside the step): the z complex-to-real transform of an x-expanded
+// chunk [f][row][kz] (row = y_local * NX + x, nkz = Nzp/3 + 1, one segment: what xfft_backward
+// writes and zphys reads) into real rows, and/or the one-point moments of u, v, w per plane
+constexpr int kMomRows = 11;  // u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4
+struct ZRealArgs {
+  int NX = 0, Nzp = 0, nkz = 0, ny = 0;   // rows = ny * NX
+  int y0 = 0;                        // global plane of the chunk's first plane (moments, U)
+  int nfields = 0;                   // transformed fields, in pairs (an odd count: the last with zero)
+  long long field_stride = 0;        // element stride between the input fields
+  // real output (T = float | double by storage precision), optional: field f with bit f of
+  // out_mask set goes to out[slot][plane][x][z], slot = its rank among the set bits
+  void* out = nullptr;
+  unsigned out_mask = 0;
+  long long out_field_stride = 0;    // real elements between slots
+  // moments (optional; needs nfields >= 3 = u, v, w): plane means over NX * Nzp points of the
+  // kMomRows products of u' = u - U(y), v, w, accumulated (+=) into moments[kMomRows][NY]
+  double* moments = nullptr;
+  const double* U = nullptr;         // device [NY]
+  int NY = 0;
+};
+void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
+
 // standalone FFT entry points for tests: batched C2C along the contiguous axis
 void fft_c2c_test(void* data, int n, int batch, int dir, const Twiddles& tw, bool fp64, hipStream_t s);
 

@@ -115,6 +115,21 @@ class Solver {
     std::vector<double> ekx, ekz, map;
   };
   Spectra spectra();
+  // Physical-space export of the current state (one rank without a communicator; not part of the
+  // step, which keeps no physical field in memory): x-backward of the K-SPEC outputs chunk by chunk
+  // into the step's scratch, then the z complex-to-real export stage (kernels.hpp zreal).
+  // physical_fields: planes `planes` (any order) of the fields `names` (u v w wx wy wz), data
+  // [name][plane][NX][Nzp]
+  struct PhysFields {
+    std::vector<int> planes;
+    std::vector<std::string> names;
+    std::vector<double> data;
+    int NX = 0, Nzp = 0;
+  };
+  PhysFields physical_fields(const std::vector<int>& planes, const std::vector<std::string>& names);
+  // plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4 (u' = u - U(y)):
+  // [kMomRows][NY], every plane
+  std::vector<double> plane_moments();
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -181,6 +196,18 @@ class Solver {
   void write_logs(const StepLog& L, bool verbose);
   void write_stats_files(const std::vector<double>& st);
   void write_spectra_files(const Spectra& sp);
+  void write_field_files();
+  void write_moment_files(const std::vector<double>& m);
+  // x-backward arguments of the whole local slab (transforms and the export): the common part, the
+  // one-rank source (sets the blocked layout in xa) and the arguments of planes [y0, y0 + ny)
+  XArgs x_args() const;
+  XSrc x_src_local(XArgs& xa) const;
+  void x_chunk(const XArgs& xa, const XSrc& src, int y0, int ny, XArgs& xc, XSrc& sc) const;
+  // export driver: the sorted distinct planes ys in contiguous runs of at most a step chunk; fields
+  // 0 .. nf-1 are transformed, those of out_mask handed to sink(y0, ny, host [slot][ny][NX][Nzp]
+  // in the storage precision), the moments accumulated into d_mom (either may be absent)
+  void export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
+                     const std::function<void(int, int, const void*)>& sink);
   void write_json(const StepLog& L, double ms_per_step);
   void wait(hipStream_t s);           // stream sync with the communicator watchdog (P > 1)
   void invalidate_graphs();
@@ -323,6 +350,9 @@ class Solver {
   void* d_spec_ = nullptr;
   void* d_sym_ = nullptr;    // kz = 0 columns (local + gathered) for the distributed symmetrisation
   size_t spec_n_ = 0;
+  void* d_real_ = nullptr;   // export: real planes of one chunk (lazily allocated)
+  size_t real_n_ = 0;
+  double* d_mom_ = nullptr;  // export: [kMomRows][NY]
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 
   bool use_graph_ = true;

@@ -210,6 +210,20 @@ void zphys(const ZArgs& a_in, void* fields, const Twiddles& tw, bool fp64, hipSt
   HIP_LAUNCH_CHECK(s);
 }
 
+void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s) {
+  CH_CHECK(tw.n == a.Nzp && tw.fp64 == fp64, "zreal: twiddle table mismatch");
+  CH_CHECK(a.nkz == a.Nzp / 3 + 1, "zreal: one segment of the 2/3 rule's retained kz (Nzp/3 + 1)");
+  CH_CHECK(a.NX >= 16, "zreal: at least 16 rows per plane");
+  CH_CHECK(a.nfields >= 1 && a.nfields <= 6, "zreal: 1 to 6 fields");
+  CH_CHECK(!a.out || ((a.out_mask >> a.nfields) == 0 && a.out_field_stride >= static_cast<long long>(a.ny) * a.NX * a.Nzp &&
+                      a.out_field_stride % (fp64 ? 2 : 4) == 0),
+           "zreal: bad output selection");
+  CH_CHECK(!a.moments || (a.nfields >= 3 && a.U && a.y0 >= 0 && a.y0 + a.ny <= a.NY), "zreal: the moments need u, v, w and U(y)");
+  if (a.ny == 0 || (!a.out && !a.moments)) return;
+  CH_DISPATCH_N(a.Nzp, fft_zr_len<NN>(a, fields, tw, fp64, s));
+  HIP_LAUNCH_CHECK(s);
+}
+
 void fft_c2c_test(void* data, int n, int batch, int dir, const Twiddles& tw, bool fp64, hipStream_t s) {
   CH_CHECK(tw.n == n && tw.fp64 == fp64, "fft_c2c_test: twiddle table mismatch");
   CH_DISPATCH_N(n, fft_test_len<NN>(data, batch, dir, tw, fp64, s));

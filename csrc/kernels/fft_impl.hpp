@@ -1851,6 +1851,160 @@ inline int ztpr_env() {
   return v;
 }
 
+// ---- z complex-to-real export (physical fields on request; one-point moments) -----------------
+// The z stage's inverse transform alone, writing the real rows instead of consuming them: the
+// fields go in pairs (Z = A + i B, as zphys), one inverse transform per pair through LDS with the
+// row geometry of zphys_kernel (zphys_tpr threads per row, zphys_rows rows per block; several rows
+// per wave below 64 threads per row, block barriers between the passes above).  Each thread then
+// takes 16 bytes of consecutive z per access: the coalesced stores of the selected fields and the
+// terms of the plane sums of u' = u - U(y), v, w (products formed in double after subtracting the
+// mean).  The sums are reduced over the row's lanes, then per plane in LDS (a block's rows may
+// belong to several planes: ZWT rows against NX >= 16 rows per plane) and leave the block as one
+// atomicAdd per (plane, moment).  One row group per block; not part of the step.
+template <typename T>
+struct alignas(16) RVec {
+  T v[16 / sizeof(T)];
+};
+template <int NZP, typename T>
+__global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(T))))
+    zreal_kernel(ZRealArgs a, const typename C2<T>::type* fields, const typename C2<T>::type* tw) {
+  using T2 = typename C2<T>::type;
+  constexpr int TPR = zphys_tpr<NZP>(sizeof(T)), ZWT = zphys_rows<NZP, T, TPR>(), NT = ZWT * TPR;
+  constexpr int PITCH = FftPitch<NZP>::value;
+  constexpr int TPRF = TPR < 64 ? 64 : TPR;     // threads per transform call (one wave or a row)
+  constexpr int RWW = TPR < 64 ? 64 / TPR : 1;  // rows per transform call
+  constexpr int TS = FftPlan<NZP>::TSIZE;
+  constexpr int nkz = NZP / 3 + 1, Kz = nkz - 1;  // (checked on the host)
+  constexpr int MK = (nkz + TPR - 1) / TPR;
+  constexpr int VEC = 16 / sizeof(T), NV = NZP / VEC, EV = (NV + TPR - 1) / TPR;
+  static_assert(NZP % VEC == 0, "rows of whole 16-byte pieces");
+  constexpr int MAXP = ZWT / 16 + 2;  // planes a block's rows can touch (NX >= 16: checked on the host)
+  __shared__ T2 s[ZWT * PITCH];
+  __shared__ T2 tws[TS];
+  __shared__ double acc[MAXP * kMomRows];
+  const int tid = threadIdx.x, t = tid % TPR, w = tid / TPR;
+  for (int i = tid; i < TS; i += NT) tws[i] = tw[i];
+  for (int i = tid; i < MAXP * kMomRows; i += NT) acc[i] = 0.0;
+  __syncthreads();
+  T2* row = s + w * PITCH;
+  T2* frow = s + (tid / TPRF) * RWW * PITCH;  // first row of this thread's transform group
+  const int ft = tid % TPRF;
+  const long long nrows = static_cast<long long>(a.ny) * a.NX;
+  const long long rfirst = static_cast<long long>(blockIdx.x) * ZWT;
+  const long long r = rfirst + w;
+  // rows past the end run the transforms on zeros (the barriers are block-uniform) and touch no
+  // global memory beyond clamped loads
+  const bool rv = r < nrows;
+  const long long rc = rv ? r : nrows - 1;
+  const int yl = static_cast<int>(rc / a.NX), pl0 = static_cast<int>(rfirst / a.NX);
+  const double Uy = a.moments ? a.U[a.y0 + yl] : 0.0;
+  const int npairs = (a.nfields + 1) / 2;
+  for (int p = 0; p < npairs; ++p) {
+    const int fa = 2 * p, fb = 2 * p + 1;
+    const bool hb = fb < a.nfields;  // an odd field count: the last field pairs with zero
+    const T2* A = fields + fa * a.field_stride + rc * nkz;
+    const T2* B = fields + (hb ? fb : fa) * a.field_stride + rc * nkz;
+    // unconditional loads at a clamped (in-bounds) index, zeros selected afterwards; Z_k = A_k + i B_k,
+    // Z_{N-k} = conj(A_k) + i conj(B_k), the kz = 0 imaginary parts dropped, zeros between
+#pragma unroll
+    for (int i = 0; i < MK; ++i) {
+      const int k = t + TPR * i;
+      const T2 x = A[min(k, Kz)], y = B[min(k, Kz)];
+      const T2 va = rv ? x : T2{0, 0}, vb = rv && hb ? y : T2{0, 0};
+      if (k < nkz) {
+        if (k == 0) {
+          row[fft_pidx(0)] = T2{va.x, vb.x};
+        } else {
+          row[fft_pidx(k)] = T2{va.x - vb.y, va.y + vb.x};
+          row[fft_pidx(NZP - k)] = T2{va.x + vb.y, vb.x - va.y};
+        }
+      }
+    }
+    for (int k = Kz + 1 + t; k < NZP - Kz; k += TPR) row[fft_pidx(k)] = T2{0, 0};
+    row_sync<TPRF>();
+    wave_fft<NZP, RWW, PITCH, true, TPRF>(frow, tws, ft);
+    const bool wa = a.out && ((a.out_mask >> fa) & 1u), wb = a.out && hb && ((a.out_mask >> fb) & 1u);
+    T* oa = static_cast<T*>(a.out) + __popc(a.out_mask & ((1u << fa) - 1u)) * a.out_field_stride + rc * NZP;
+    T* ob = static_cast<T*>(a.out) + __popc(a.out_mask & ((1u << fb) - 1u)) * a.out_field_stride + rc * NZP;
+    const bool mom = a.moments && p < 2;
+    double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < EV; ++i) {
+      const int nv = t + TPR * i;
+      if (NV % TPR == 0 || nv < NV) {
+        RVec<T> ra, rb;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const T2 z = row[fft_pidx(nv * VEC + j)];
+          ra.v[j] = z.x;
+          rb.v[j] = z.y;
+        }
+        if (rv) {
+          if (wa) *reinterpret_cast<RVec<T>*>(oa + nv * VEC) = ra;
+          if (wb) *reinterpret_cast<RVec<T>*>(ob + nv * VEC) = rb;
+          if (mom) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+              if (p == 0) {  // (u, v)
+                const double du = static_cast<double>(ra.v[j]) - Uy, dv = static_cast<double>(rb.v[j]);
+                const double uu = du * du, vv = dv * dv;
+                m[0] += du;
+                m[1] += uu;
+                m[2] += vv;
+                m[3] += du * dv;
+                m[4] += uu * du;
+                m[5] += vv * dv;
+                m[6] += uu * uu;
+                m[7] += vv * vv;
+              } else {  // (w, omega_x)
+                const double dw = static_cast<double>(ra.v[j]), ww = dw * dw;
+                m[0] += ww;
+                m[1] += ww * dw;
+                m[2] += ww * ww;
+              }
+            }
+          }
+        }
+      }
+    }
+    if (mom) {  // (block-uniform)
+      // moment rows of the pair's sums (kMomRows order)
+      constexpr int kRow0[8] = {0, 1, 2, 4, 5, 6, 8, 9}, kRow1[3] = {3, 7, 10};
+      const int nm = p == 0 ? 8 : 3;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if (q < nm) {
+          double v = m[q];
+#pragma unroll
+          for (int o = (TPR < 64 ? TPR : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+          if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&acc[(yl - pl0) * kMomRows + (p == 0 ? kRow0[q] : kRow1[q % 3])], v);
+        }
+      }
+    }
+    row_sync<TPRF>();  // this pair's LDS reads precede the next pair's writes
+  }
+  if (a.moments) {
+    __syncthreads();
+    const int pl1 = static_cast<int>(min(nrows - 1, rfirst + ZWT - 1) / a.NX);  // last plane of the block's rows
+    const double sc = 1.0 / (static_cast<double>(a.NX) * NZP);
+    for (int i = tid; i < MAXP * kMomRows; i += NT) {
+      const int pl = pl0 + i / kMomRows;
+      if (pl <= pl1) atomicAdd(&a.moments[(i % kMomRows) * a.NY + a.y0 + pl], acc[i] * sc);
+    }
+  }
+}
+
+template <int NN, typename T>
+static void zreal_launch(const ZRealArgs& a, const void* fields, const Twiddles& tw, hipStream_t s) {
+  using T2 = typename C2<T>::type;
+  constexpr int ZR = zphys_rows<NN, T>(), TPR = zphys_tpr<NN>(sizeof(T));
+  const long long nrows = static_cast<long long>(a.ny) * a.NX;
+  const long long ngroups = (nrows + ZR - 1) / ZR;
+  CH_CHECK(ngroups < (1LL << 31), "zreal: too many rows for one launch");
+  hipLaunchKernelGGL((zreal_kernel<NN, T>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
+                     static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
+}
+
 // ---- standalone batched C2C (tests) ----------------------------------------------------------
 template <int N, typename T, bool INV>
 __global__ void __launch_bounds__(256) fft_test_kernel(typename C2<T>::type* data, int batch,
@@ -1910,6 +2064,11 @@ void fft_zp_len(const ZArgs& a, void* fields, const Twiddles& tw, bool fp64, hip
   else fft_zp_len_t<NN, float>(a, fields, tw, s);
 }
 template <int NN>
+void fft_zr_len(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s) {
+  if (fp64) zreal_launch<NN, double>(a, fields, tw, s);
+  else zreal_launch<NN, float>(a, fields, tw, s);
+}
+template <int NN>
 void fft_test_len(void* data, int batch, int dir, const Twiddles& tw, bool fp64, hipStream_t s) {
   dim3 grid((batch + 3) / 4);
   if (fp64) {
@@ -1935,12 +2094,14 @@ void fft_test_len(void* data, int batch, int dir, const Twiddles& tw, bool fp64,
   template void fft_xb_len<NN>(const XArgs&, const XSrc&, void*, const Twiddles&, bool, hipStream_t);      \
   template void fft_xf_len<NN>(const XArgs&, const void*, const XDst&, const Twiddles&, bool, hipStream_t); \
   template void fft_zp_len<NN>(const ZArgs&, void*, const Twiddles&, bool, hipStream_t);                    \
+  template void fft_zr_len<NN>(const ZRealArgs&, const void*, const Twiddles&, bool, hipStream_t);          \
   template void fft_test_len<NN>(void*, int, int, const Twiddles&, bool, hipStream_t);
 // (extern declarations per entry point: an extern template covers one declaration)
 #define CH_FFT_EXTERN_ALL(NN)                                                                                   \
   extern template void fft_xb_len<NN>(const XArgs&, const XSrc&, void*, const Twiddles&, bool, hipStream_t);      \
   extern template void fft_xf_len<NN>(const XArgs&, const void*, const XDst&, const Twiddles&, bool, hipStream_t); \
   extern template void fft_zp_len<NN>(const ZArgs&, void*, const Twiddles&, bool, hipStream_t);                    \
+  extern template void fft_zr_len<NN>(const ZRealArgs&, const void*, const Twiddles&, bool, hipStream_t);          \
   extern template void fft_test_len<NN>(void*, int, int, const Twiddles&, bool, hipStream_t);
 CH_FFT_POW2_LENGTHS(CH_FFT_EXTERN_ALL)
 CH_FFT_R3_LENGTHS(CH_FFT_EXTERN_ALL)
