@@ -58,7 +58,7 @@ class ChannelFlow:
         self.rank, self.world, self.device = rank, world, device
         self.solver = C.Solver(cfg, rank, world, device, uid)
         self.cfg = cfg
-        self.statistics = TurbulenceStatistics(np.asarray(self.solver.grid.y), 1.0 / cfg.Re)
+        self.statistics = TurbulenceStatistics(np.asarray(self.solver.grid.y), 1.0 / cfg.Re, cfg.stretch)
 
     # ---- setup -----------------------------------------------------------------------------
     @property
@@ -124,11 +124,24 @@ class ChannelFlow:
         u' = u - U(y): ``ndarray (11, NY)`` (``statistics.MOMENT_ROWS``)."""
         return np.asarray(self.solver.plane_moments())
 
+    def gradient_sums(self) -> np.ndarray:
+        """Velocity-gradient plane sums of the current state, ``ndarray (7, NY)``
+        (``statistics.GRADIENT_ROWS``): <|wx|^2>, <|wy|^2>, <|wz|^2> and g_uu, g_vv, g_ww, g_uv with
+        g_ab = <grad a' . grad b'> -- raw sums, no nu and no factor 2.  Any number of ranks."""
+        return np.asarray(self.solver.gradient_sums())
+
+    def transport_moments(self) -> np.ndarray:
+        """Plane means of u'u'v, wwv, u'vv (``statistics.TRANSPORT_ROWS``): ``ndarray (3, NY)``;
+        one rank without a communicator, like ``plane_moments`` (which has <v^3> in row 6)."""
+        return np.asarray(self.solver.transport_moments())
+
     # ---- time-averaged statistics -------------------------------------------------------------
-    def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False):
+    def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
-        ``moments``: also the third and fourth central moments (skewness / flatness profiles)."""
+        ``moments``: also the third and fourth central moments (skewness / flatness profiles);
+        ``budgets``: also the velocity-gradient sums and the triple products (vorticity r.m.s. and
+        the budgets of k and the Reynolds stresses; takes the plane moments too, for <v^3>)."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -139,8 +152,11 @@ class ChannelFlow:
                 L = self.solver.log()
                 self.statistics.add(np.asarray(self.solver.mean_profile()), np.asarray(self.solver.stats()), L.utau_lo,
                                     L.utau_hi, L.time)
+                m = self.plane_moments() if (moments or budgets) else None
                 if moments:
-                    self.statistics.add_moments(self.plane_moments())
+                    self.statistics.add_moments(m)
+                if budgets:
+                    self.statistics.add_budgets(self.gradient_sums(), self.transport_moments(), m[6])
         return self.statistics
 
     def grid_points(self) -> int:

@@ -8,7 +8,10 @@ plane sums, all ranks reduced) and the wall friction velocities — and produces
 wall-unit profiles folded over the two channel halves: U+(y+), u'+, v'+, w'+ r.m.s., -<u'v'>+,
 plus the scalar checks of a statistically steady Re_tau~180 channel (Re_tau, U+_c, the u'+ peak
 and its y+).  Optionally it also averages the one-point central moments of the physical-space
-export (``Solver.plane_moments``) into skewness and flatness profiles of u, v, w.
+export (``Solver.plane_moments``) into skewness and flatness profiles of u, v, w, and the
+velocity-gradient sums (``Solver.gradient_sums``) and triple products (``Solver.transport_moments``)
+into vorticity r.m.s. profiles and the budgets of k and of the Reynolds stresses (without the
+pressure terms: the phi / omega_y formulation carries no pressure).
 """
 from __future__ import annotations
 
@@ -19,12 +22,18 @@ import numpy as np
 
 # rows of Solver.plane_moments()
 MOMENT_ROWS = ("u", "uu", "vv", "ww", "uv", "uuu", "vvv", "www", "uuuu", "vvvv", "wwww")
+# rows of Solver.gradient_sums() and Solver.transport_moments()
+GRADIENT_ROWS = ("wxwx", "wywy", "wzwz", "guu", "gvv", "gww", "guv")
+TRANSPORT_ROWS = ("uuv", "wwv", "uvv")
+BUDGET_STRESSES = ("k", "uu", "vv", "ww", "uv")
+BUDGET_TERMS = ("prod", "eps", "visc", "turb", "resid")
 
 
 class TurbulenceStatistics:
-    def __init__(self, y: np.ndarray, nu: float):
+    def __init__(self, y: np.ndarray, nu: float, stretch: float = 2.0):
         self.y = np.asarray(y, float)
         self.nu = float(nu)
+        self.stretch = float(stretch)  # of the tanh grid (the budgets' compact D1, D2)
         self.reset()
 
     def reset(self):
@@ -37,6 +46,62 @@ class TurbulenceStatistics:
         self.t1 = None
         self.nm = 0
         self.mom = np.zeros((len(MOMENT_ROWS), n))
+        self.nb = 0
+        self.grad = np.zeros((len(GRADIENT_ROWS), n))
+        self.triple = np.zeros((len(TRANSPORT_ROWS), n))
+        self.vvv = np.zeros(n)
+
+    def add_budgets(self, grad, triple, vvv):
+        """One sample of the velocity-gradient sums [7, NY] (``GRADIENT_ROWS``), the triple products
+        [3, NY] (``TRANSPORT_ROWS``) and <v^3> [NY] (row 6 of the plane moments).  The budgets are
+        formed from the averages, together with U and the second moments of ``add``."""
+        n = self.y.size
+        self.grad += np.asarray(grad, float).reshape(len(GRADIENT_ROWS), n)
+        self.triple += np.asarray(triple, float).reshape(len(TRANSPORT_ROWS), n)
+        self.vvv += np.asarray(vvv, float).reshape(n)
+        self.nb += 1
+
+    def budgets(self) -> dict:
+        """Unfolded budget terms over all NY points in solver units: ``{term_stress: ndarray (NY,)}``
+        for the terms prod, eps, visc, turb, resid of k = (uu + vv + ww) / 2, uu, vv, ww, uv:
+
+          prod   P_k = -<u'v> U', P_uu = -2 <u'v> U', P_uv = -<vv> U', P_vv = P_ww = 0
+          eps    nu (g_uu + g_vv + g_ww) for k; 2 nu g for uu, vv, ww, uv
+          visc   nu D2 <.>
+          turb   -D1 of (uuv + vvv + wwv) / 2, uuv, vvv, wwv, uvv
+          resid  -(prod - eps + visc + turb)
+
+        ``resid`` is what closes the balance: the pressure terms (pressure diffusion and pressure
+        strain, which this formulation cannot form) plus the unsteadiness of the finite average.
+        D1 and D2 are the dense compact operators of ``reference.oracle.build_ops``."""
+        if self.n == 0 or self.nb == 0:
+            raise ValueError("no budget samples")
+        from ..reference.oracle import build_ops
+
+        ops = build_ops(self.y.size, self.stretch)
+        if not np.allclose(ops.y, self.y, rtol=0, atol=1e-12):
+            raise ValueError("the grid is not the tanh grid of this stretch: pass stretch= to TurbulenceStatistics")
+        nu = self.nu
+        U = self.U / self.n
+        uu, vv, ww, uv = self.ms / self.n
+        g = self.grad / self.nb
+        uuv, wwv, uvv = self.triple / self.nb
+        vvv = self.vvv / self.nb
+        dU = ops.D1 @ U
+        zero = np.zeros_like(U)
+        stress = {"k": 0.5 * (uu + vv + ww), "uu": uu, "vv": vv, "ww": ww, "uv": uv}
+        prod = {"k": -uv * dU, "uu": -2.0 * uv * dU, "vv": zero, "ww": zero, "uv": -vv * dU}
+        eps = {"k": nu * (g[3] + g[4] + g[5]), "uu": 2 * nu * g[3], "vv": 2 * nu * g[4], "ww": 2 * nu * g[5],
+               "uv": 2 * nu * g[6]}
+        flux = {"k": 0.5 * (uuv + vvv + wwv), "uu": uuv, "vv": vvv, "ww": wwv, "uv": uvv}
+        out = {}
+        for s in BUDGET_STRESSES:
+            out["prod_" + s] = prod[s]
+            out["eps_" + s] = eps[s]
+            out["visc_" + s] = nu * (ops.D2 @ stress[s])
+            out["turb_" + s] = -(ops.D1 @ flux[s])
+            out["resid_" + s] = -(prod[s] - eps[s] + out["visc_" + s] + out["turb_" + s])
+        return out
 
     def add_moments(self, m):
         """One sample of the raw central moments [11, NY] (``MOMENT_ROWS``); the moments are
@@ -92,6 +157,17 @@ class TurbulenceStatistics:
                 # v-skewness is antisymmetric about the centreline (v -> -v under the reflection)
                 out["skew_" + q] = fold(np.where(ok, mom[r3] / d ** 1.5, 0.0), -1.0 if q == "v" else 1.0)
                 out["flat_" + q] = fold(np.where(ok, mom[r4] / d ** 2, 0.0))
+        if self.nb:
+            g = self.grad / self.nb
+            # vorticity r.m.s. in units of u_tau^2 / nu
+            for q, name in enumerate(("wx_rms", "wy_rms", "wz_rms")):
+                out[name] = np.sqrt(np.maximum(fold(g[q]), 0.0)) * self.nu / ut ** 2
+            # budgets in units of u_tau^4 / nu; under the reflection y -> -y (v -> -v, d/dy -> -d/dy)
+            # every term of the k, uu, vv, ww budgets is symmetric and every term of the uv budget
+            # antisymmetric (folded like -<u'v'>: the lower half's orientation)
+            sc = self.nu / ut ** 4
+            for k, a in self.budgets().items():
+                out[k] = sc * fold(a, -1.0 if k.endswith("_uv") else 1.0)
         return out
 
     def summary(self) -> dict:
@@ -124,6 +200,10 @@ class TurbulenceStatistics:
         names = "y yplus Uplus urms_plus vrms_plus wrms_plus minus_uv_plus"
         if self.nm:
             extra = ["skew_u", "skew_v", "skew_w", "flat_u", "flat_v", "flat_w"]
+            cols += [p[k] for k in extra]
+            names += " " + " ".join(extra)
+        if self.nb:
+            extra = ["wx_rms", "wy_rms", "wz_rms"] + [f"{t}_{s}" for s in BUDGET_STRESSES for t in BUDGET_TERMS]
             cols += [p[k] for k in extra]
             names += " " + " ".join(extra)
         cols = np.column_stack(cols)

@@ -73,7 +73,7 @@ PYBIND11_MODULE(_core, m) {
       RW(symmetry_every) RW(checkpoint_every) RW(log_every) RW(precision) RW(decomposition) RW(pr) RW(pc) RW(seed)
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
-      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every);
+      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -278,7 +278,32 @@ PYBIND11_MODULE(_core, m) {
              std::copy(m.begin(), m.end(), a.mutable_data());
              return a;
            },
-           "plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4: (11, NY) (one rank)");
+           "plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4: (11, NY) (one rank)")
+      .def("gradient_sums",
+           [](Solver& s) {
+             std::vector<double> g;
+             {
+               py::gil_scoped_release r;
+               g = s.gradient_sums();
+             }
+             py::array_t<double> a({static_cast<py::ssize_t>(kGradRows), static_cast<py::ssize_t>(s.plan().NY)});
+             std::copy(g.begin(), g.end(), a.mutable_data());
+             return a;
+           },
+           "velocity-gradient plane sums wxwx, wywy, wzwz, guu, gvv, gww, guv of the current state: (7, NY), "
+           "raw sums (no nu, no factor 2), global over the communicator")
+      .def("transport_moments",
+           [](Solver& s) {
+             std::vector<double> t;
+             {
+               py::gil_scoped_release r;
+               t = s.transport_moments();
+             }
+             py::array_t<double> a({static_cast<py::ssize_t>(kTripleRows), static_cast<py::ssize_t>(s.plan().NY)});
+             std::copy(t.begin(), t.end(), a.mutable_data());
+             return a;
+           },
+           "plane means of u'u'v, wwv, u'vv: (3, NY) (one rank)");
 
   py::class_<ProcInfo>(m, "ProcInfo")
       .def(py::init<>())

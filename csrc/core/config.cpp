@@ -226,6 +226,7 @@ Config Config::from_tree(const ConfigTree& t) {
   c.fields_planes = t.get_string(pick(t, "fields_planes"), c.fields_planes);
   c.fields = t.get_string(pick(t, "fields"), c.fields);
   c.moments_every = static_cast<int>(t.get_int(pick(t, "moments_every"), c.moments_every));
+  c.budget_every = static_cast<int>(t.get_int(pick(t, "budget_every"), c.budget_every));
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -321,7 +322,8 @@ void Config::validate() const {
   CH_CHECK(ic == "random" || ic == "laminar" || ic == "file" || ic == "os_mode" || ic == "zero",
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
-               spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0,
+               spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
+               budget_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
   CH_CHECK(rollback_cfl_factor > 0 && rollback_cfl_factor <= 1, "rollback_cfl_factor must be in (0, 1]");
@@ -361,6 +363,7 @@ std::string Config::to_string() const {
   o << "  spectra_planes = \"" << spectra_planes << "\";\n  log_json = \"" << log_json << "\";\n";
   o << "  fields_every = " << fields_every << ";\n  fields_planes = \"" << fields_planes << "\";\n";
   o << "  fields = \"" << fields << "\";\n  moments_every = " << moments_every << ";\n";
+  o << "  budget_every = " << budget_every << ";\n";
   o << "};\n";
   return o.str();
 }

@@ -451,10 +451,12 @@ void Solver::free_all() {
   if (h_tdt_) (void)hipHostFree(h_tdt_);
   h_tdt_ = nullptr;
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
-                  static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_)})
+                  static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
+                  static_cast<void*>(d_grad_)})
     if (p) (void)hipFree(p);
   state_ = out_ = phys_ = xbuf_ = zbuf_ = dscal_ = snap_ = d_spec_ = d_sym_ = d_real_ = nullptr;
   d_mom_ = nullptr;
+  d_grad_ = nullptr;
   real_n_ = 0;
   d_rowtab_ = nullptr;
   d_y_ = nullptr;
@@ -2160,6 +2162,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (pe > 0 && nstep_ % pe == 0) write_spectra_files(spectra());
     if (cfg_.fields_every > 0 && nstep_ % cfg_.fields_every == 0) write_field_files();
     if (cfg_.moments_every > 0 && nstep_ % cfg_.moments_every == 0) write_moment_files(plane_moments());
+    if (cfg_.budget_every > 0 && nstep_ % cfg_.budget_every == 0) write_budget_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();
       prepare();
@@ -2372,7 +2375,7 @@ void Solver::write_spectra_files(const Spectra& sp) {
 // the blocked layout, planes past ny clamped at the loads and masked at the stores (also in the
 // plane tiles of the wide kernels), so a run of planes is transformed as it is requested.
 void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
-                           const std::function<void(int, int, const void*)>& sink) {
+                           const std::function<void(int, int, const void*)>& sink, double* d_triple) {
   CH_CHECK(!comm_, "physical-space export is single-rank: it needs a solver without a communicator");
   const Plan& p = plan_;
   if (!prepared_) prepare();
@@ -2417,6 +2420,7 @@ void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask
     za.out_mask = out_mask;
     za.out_field_stride = static_cast<long long>(ny * plane);
     za.moments = d_mom;
+    za.triple = d_triple;
     za.U = d_mean_;
     za.NY = p.NY;
     zreal(za, phys_, tw_z_, fp64_, s_comp_);
@@ -2477,8 +2481,8 @@ Solver::PhysFields Solver::physical_fields(const std::vector<int>& planes, const
 std::vector<double> Solver::plane_moments() {
   CH_CHECK(!comm_, "plane_moments: the export is single-rank (a solver without a communicator)");
   const Plan& p = plan_;
-  const size_t n = static_cast<size_t>(kMomRows) * p.NY;
-  if (!d_mom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_mom_), n * sizeof(double)));
+  const size_t n = static_cast<size_t>(kMomRows) * p.NY, na = static_cast<size_t>(kMomRows + kTripleRows) * p.NY;
+  if (!d_mom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_mom_), na * sizeof(double)));
   if (!prepared_) prepare();
   HIP_CHECK(hipMemsetAsync(d_mom_, 0, n * sizeof(double), s_comp_));
   std::vector<int> ys(p.NY);
@@ -2488,6 +2492,98 @@ std::vector<double> Solver::plane_moments() {
   HIP_CHECK(hipMemcpyAsync(m.data(), d_mom_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
   HIP_CHECK(hipStreamSynchronize(s_comp_));
   return m;
+}
+
+// the mixed triple products of the turbulent-transport terms: the export stage over every plane
+// with the (w, v) second pair (kernels.hpp ZRealArgs::triple); the moments it forms on the way are
+// dropped
+std::vector<double> Solver::transport_moments() {
+  CH_CHECK(!comm_, "transport_moments: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const size_t n = static_cast<size_t>(kMomRows) * p.NY, nt = static_cast<size_t>(kTripleRows) * p.NY;
+  if (!d_mom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_mom_), (n + nt) * sizeof(double)));
+  if (!prepared_) prepare();
+  HIP_CHECK(hipMemsetAsync(d_mom_, 0, (n + nt) * sizeof(double), s_comp_));
+  std::vector<int> ys(p.NY);
+  for (int j = 0; j < p.NY; ++j) ys[j] = j;
+  export_planes(ys, 3, 0u, d_mom_, nullptr, d_mom_ + n);
+  std::vector<double> m(nt);
+  HIP_CHECK(hipMemcpyAsync(m.data(), d_mom_ + n, nt * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  return m;
+}
+
+// ---- velocity-gradient sums -----------------------------------------------------------------------
+// As spectra(): K-SPEC's outputs of the current state are read in place, one launch per kx
+// sub-block on the compute stream behind whatever is queued; nothing the next step reads is
+// written, so the step graphs stay valid.
+std::vector<double> Solver::gradient_sums() {
+  const Plan& p = plan_;
+  const size_t n = static_cast<size_t>(kGradRows) * p.NY;
+  if (!d_grad_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_grad_), n * sizeof(double)));
+  if (!prepared_) prepare();
+  HIP_CHECK(hipMemsetAsync(d_grad_, 0, n * sizeof(double), s_comp_));
+  GradSumArgs a;
+  const int nf = bwd_fields();
+  for (int f = 0; f < nf; ++f) a.f[f] = in_field(f);
+  a.combine = combine_ ? 1 : 0;
+  a.ax = p.ax;
+  a.az = p.az;
+  a.N = p.NY;
+  a.nkz_loc = p.nkz_loc;
+  a.kz0 = p.kz0;
+  a.nkzs = nkzs_;
+  a.kzb = kzb_;
+  a.nkx = p.nkx;
+  a.Kx = p.Kx;
+  a.sums = d_grad_;
+  for (int b = 0; b < nkb_; ++b) {
+    GradSumArgs ab = a;
+    for (int f = 0; f < nf; ++f) ab.f[f] = static_cast<const char*>(a.f[f]) + kb_off_[b] * esz_;
+    ab.nkx_loc = kb_cnt_[b];
+    ab.kx0 = p.kx0 + kb_start_[b];
+    gradsum_accumulate(ab, fp64_, s_comp_);
+  }
+  if (comm_) {
+    HIP_CHECK(hipEventRecord(ev_stats_, s_comp_));
+    HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_stats_, 0));
+    comm_->allreduce_sum_f64(d_grad_, n, s_comm_);
+    wait(s_comm_);
+  }
+  std::vector<double> g(n);
+  HIP_CHECK(hipMemcpyAsync(g.data(), d_grad_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
+  wait(s_comp_);
+  return g;
+}
+
+// one line of NY values per call and file, as write_stats_files: the vorticity r.m.s., the
+// dissipation 2 nu g of the uu, vv, ww, uv budgets and (one rank without a communicator) the triple
+// products of the turbulent transport
+void Solver::write_budget_files() {
+  const std::vector<double> g = gradient_sums();
+  std::vector<double> t;
+  if (!comm_) {
+    t = transport_moments();
+  } else if (!budget_note_ && plan_.rank == 0) {
+    std::fprintf(stderr, "[channel] budget_every: TRIPLE_*.dat skipped (the physical-space export is single-rank)\n");
+    budget_note_ = true;
+  }
+  if (plan_.rank != 0) return;
+  const int N = plan_.NY;
+  const double nu = 1.0 / cfg_.Re;
+  auto line = [&](const char* name, const double* v, double scale, bool root) {
+    std::ofstream f(cfg_.path + name, std::ios::app);
+    f.precision(8);
+    for (int j = 0; j < N; ++j) f << " " << std::scientific << (root ? std::sqrt(std::max(0.0, v[j])) : scale * v[j]);
+    f << " \n";
+  };
+  const char* wn[3] = {"WXRMS.dat", "WYRMS.dat", "WZRMS.dat"};
+  const char* en[4] = {"EPS_UU.dat", "EPS_VV.dat", "EPS_WW.dat", "EPS_UV.dat"};
+  const char* tn[3] = {"TRIPLE_UUV.dat", "TRIPLE_WWV.dat", "TRIPLE_UVV.dat"};
+  for (int q = 0; q < 3; ++q) line(wn[q], g.data() + q * N, 1.0, true);
+  for (int q = 0; q < 4; ++q) line(en[q], g.data() + (3 + q) * N, 2.0 * nu, false);
+  if (!t.empty())
+    for (int q = 0; q < 3; ++q) line(tn[q], t.data() + q * N, 1.0, false);
 }
 
 // One NumPy v1.0 file per field, <path>FIELD_<name>_<step>.npy of shape (nplanes, NX, Nzp) in the

@@ -89,6 +89,7 @@ struct Config {
   int fields_every = 0;                // 0 = off; FIELD_<name>_<step>.npy planes + FIELDS_<step>.json
   std::string fields_planes = "";      // comma-separated y indices ("" = every plane)
   std::string fields = "u,v,w";        // of u, v, w, wx, wy, wz
+  int budget_every = 0;                // 0 = off; vorticity r.m.s., dissipation and triple-product profiles (W?RMS.dat, EPS_*.dat, TRIPLE_*.dat)
   int moments_every = 0;               // 0 = off; skewness / flatness profiles of u, v, w (*SKEW.dat, *FLAT.dat)
 
   static Config from_tree(const ConfigTree& t);

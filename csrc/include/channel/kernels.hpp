@@ -263,7 +263,12 @@ struct ZRealArgs {
   double* moments = nullptr;
   const double* U = nullptr;         // device [NY]
   int NY = 0;
+  // mixed triple products (optional; with moments, nfields == 3 and no real output): plane means of
+  // u'u'v, w w v, u'v v accumulated (+=) into triple[kTripleRows][NY].  The second pair is then
+  // transformed as (w, v) instead of (w, 0), so w and v meet in the same registers.
+  double* triple = nullptr;
 };
+constexpr int kTripleRows = 3;  // u'u'v, wwv, u'vv
 void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
 
 // standalone FFT entry points for tests: batched C2C along the contiguous axis
@@ -315,6 +320,26 @@ struct SpectraArgs {
 };
 // accumulates (+=) into ekx/ekz; map is overwritten for the local block
 void spectra_accumulate(const SpectraArgs& a, bool fp64, hipStream_t s);
+// Velocity-gradient plane sums of the current state (vorticity r.m.s., dissipation): every plane of
+// one local block of spectral fields is read once and kGradRows Parseval sums per plane are
+// accumulated (+=) into sums[kGradRows][N].  Weights as SpectraArgs (kz = 0 once, kz > 0 twice, the
+// mean line skipped); the wall-normal derivatives are the solver's own, D u = i al v - omega_z,
+// D w = omega_x + i be v, D v = -i (al u + be w), so no y-solve is needed.  Rows: |omega_x|^2,
+// |omega_y|^2, |omega_z|^2, g_uu = k2 |u|^2 + |D u|^2, g_vv, g_ww, g_uv = k2 Re(u v*) + Re(Du Dv*).
+constexpr int kGradRows = 7;
+struct GradSumArgs {
+  // six-output mode: u, v, w, omega_x, omega_y (the omega state), omega_z; combine mode: D1 v, v,
+  // D1 omega, omega, phi (f[5] unused), from which u, w, omega_x, omega_z are formed per element
+  const void* f[6] = {};
+  int combine = 0;
+  double ax = 1.0, az = 2.0;
+  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
+  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
+  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
+  int nkx = 0, Kx = 0;                // global retained kx count
+  double* sums = nullptr;             // [kGradRows][N]
+};
+void gradsum_accumulate(const GradSumArgs& a, bool fp64, hipStream_t s);
 // fault injection (tests): element `elem` of a complex field becomes NaN
 void inject_nan(void* field, size_t elem, bool fp64, hipStream_t s);
 

@@ -130,6 +130,13 @@ class Solver {
   // plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4 (u' = u - U(y)):
   // [kMomRows][NY], every plane
   std::vector<double> plane_moments();
+  // Velocity-gradient plane sums of the current state, [kGradRows][NY] (kernels.hpp GradSumArgs:
+  // |omega_x|^2, |omega_y|^2, |omega_z|^2, g_uu, g_vv, g_ww, g_uv; raw sums, no nu and no factor 2),
+  // global (any communicator; all-reduced like spectra())
+  std::vector<double> gradient_sums();
+  // plane means of u'u'v, wwv, u'vv, [kTripleRows][NY] (one rank without a communicator, through the
+  // export stage like plane_moments)
+  std::vector<double> transport_moments();
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -198,6 +205,7 @@ class Solver {
   void write_spectra_files(const Spectra& sp);
   void write_field_files();
   void write_moment_files(const std::vector<double>& m);
+  void write_budget_files();
   // x-backward arguments of the whole local slab (transforms and the export): the common part, the
   // one-rank source (sets the blocked layout in xa) and the arguments of planes [y0, y0 + ny)
   XArgs x_args() const;
@@ -207,7 +215,7 @@ class Solver {
   // 0 .. nf-1 are transformed, those of out_mask handed to sink(y0, ny, host [slot][ny][NX][Nzp]
   // in the storage precision), the moments accumulated into d_mom (either may be absent)
   void export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
-                     const std::function<void(int, int, const void*)>& sink);
+                     const std::function<void(int, int, const void*)>& sink, double* d_triple = nullptr);
   void write_json(const StepLog& L, double ms_per_step);
   void wait(hipStream_t s);           // stream sync with the communicator watchdog (P > 1)
   void invalidate_graphs();
@@ -352,7 +360,9 @@ class Solver {
   size_t spec_n_ = 0;
   void* d_real_ = nullptr;   // export: real planes of one chunk (lazily allocated)
   size_t real_n_ = 0;
-  double* d_mom_ = nullptr;  // export: [kMomRows][NY]
+  double* d_mom_ = nullptr;  // export: [kMomRows][NY], then [kTripleRows][NY]
+  double* d_grad_ = nullptr;  // gradient sums: [kGradRows][NY]
+  bool budget_note_ = false;  // the "triple files skipped" note has been printed
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 
   bool use_graph_ = true;

@@ -1861,6 +1861,9 @@ inline int ztpr_env() {
 // mean).  The sums are reduced over the row's lanes, then per plane in LDS (a block's rows may
 // belong to several planes: ZWT rows against NX >= 16 rows per plane) and leave the block as one
 // atomicAdd per (plane, moment).  One row group per block; not part of the step.
+// With ZRealArgs::triple the second pair is (w, v) instead of (w, 0) and the mixed triple products
+// u'u'v, u'vv (first pair) and wwv (second pair) are summed beside the moments, from the same
+// registers and through the same reduction.
 template <typename T>
 struct alignas(16) RVec {
   T v[16 / sizeof(T)];
@@ -1881,10 +1884,11 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
   constexpr int MAXP = ZWT / 16 + 2;  // planes a block's rows can touch (NX >= 16: checked on the host)
   __shared__ T2 s[ZWT * PITCH];
   __shared__ T2 tws[TS];
-  __shared__ double acc[MAXP * kMomRows];
+  constexpr int kAccRows = kMomRows + kTripleRows;  // per plane: the moments, then the triple products
+  __shared__ double acc[MAXP * kAccRows];
   const int tid = threadIdx.x, t = tid % TPR, w = tid / TPR;
   for (int i = tid; i < TS; i += NT) tws[i] = tw[i];
-  for (int i = tid; i < MAXP * kMomRows; i += NT) acc[i] = 0.0;
+  for (int i = tid; i < MAXP * kAccRows; i += NT) acc[i] = 0.0;
   __syncthreads();
   T2* row = s + w * PITCH;
   T2* frow = s + (tid / TPRF) * RWW * PITCH;  // first row of this thread's transform group
@@ -1900,8 +1904,9 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
   const double Uy = a.moments ? a.U[a.y0 + yl] : 0.0;
   const int npairs = (a.nfields + 1) / 2;
   for (int p = 0; p < npairs; ++p) {
-    const int fa = 2 * p, fb = 2 * p + 1;
-    const bool hb = fb < a.nfields;  // an odd field count: the last field pairs with zero
+    const bool tv = a.triple && p == 1;  // triple products: w pairs with v (the host checks nfields == 3)
+    const int fa = 2 * p, fb = tv ? 1 : 2 * p + 1;
+    const bool hb = tv || fb < a.nfields;  // an odd field count: the last field pairs with zero
     const T2* A = fields + fa * a.field_stride + rc * nkz;
     const T2* B = fields + (hb ? fb : fa) * a.field_stride + rc * nkz;
     // unconditional loads at a clamped (in-bounds) index, zeros selected afterwards; Z_k = A_k + i B_k,
@@ -1928,6 +1933,7 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
     T* ob = static_cast<T*>(a.out) + __popc(a.out_mask & ((1u << fb) - 1u)) * a.out_field_stride + rc * NZP;
     const bool mom = a.moments && p < 2;
     double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double tr[2] = {0, 0};  // (u, v): u'u'v, u'vv; (w, v): wwv
 #pragma unroll
     for (int i = 0; i < EV; ++i) {
       const int nv = t + TPR * i;
@@ -1956,11 +1962,16 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
                 m[5] += vv * dv;
                 m[6] += uu * uu;
                 m[7] += vv * vv;
+                if (a.triple) {
+                  tr[0] += uu * dv;
+                  tr[1] += du * vv;
+                }
               } else {  // (w, omega_x)
                 const double dw = static_cast<double>(ra.v[j]), ww = dw * dw;
                 m[0] += ww;
                 m[1] += ww * dw;
                 m[2] += ww * ww;
+                if (a.triple) tr[0] += ww * static_cast<double>(rb.v[j]);
               }
             }
           }
@@ -1977,7 +1988,19 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
           double v = m[q];
 #pragma unroll
           for (int o = (TPR < 64 ? TPR : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-          if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&acc[(yl - pl0) * kMomRows + (p == 0 ? kRow0[q] : kRow1[q % 3])], v);
+          if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&acc[(yl - pl0) * kAccRows + (p == 0 ? kRow0[q] : kRow1[q % 3])], v);
+        }
+      }
+      if (a.triple) {  // (block-uniform) rows u'u'v, wwv, u'vv behind the plane's moments
+        const int nt = p == 0 ? 2 : 1;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          if (q < nt) {
+            double v = tr[q];
+#pragma unroll
+            for (int o = (TPR < 64 ? TPR : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&acc[(yl - pl0) * kAccRows + kMomRows + (p == 0 ? 2 * q : 1)], v);
+          }
         }
       }
     }
@@ -1987,9 +2010,12 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
     __syncthreads();
     const int pl1 = static_cast<int>(min(nrows - 1, rfirst + ZWT - 1) / a.NX);  // last plane of the block's rows
     const double sc = 1.0 / (static_cast<double>(a.NX) * NZP);
-    for (int i = tid; i < MAXP * kMomRows; i += NT) {
-      const int pl = pl0 + i / kMomRows;
-      if (pl <= pl1) atomicAdd(&a.moments[(i % kMomRows) * a.NY + a.y0 + pl], acc[i] * sc);
+    for (int i = tid; i < MAXP * kAccRows; i += NT) {
+      const int pl = pl0 + i / kAccRows, q = i % kAccRows;
+      if (pl <= pl1) {
+        if (q < kMomRows) atomicAdd(&a.moments[q * a.NY + a.y0 + pl], acc[i] * sc);
+        else if (a.triple) atomicAdd(&a.triple[(q - kMomRows) * a.NY + a.y0 + pl], acc[i] * sc);
+      }
     }
   }
 }

@@ -1,5 +1,6 @@
-"""Cost of one plane_moments() and one three-field all-plane physical_fields() at 1024x385x1024 fp32,
-relative to one RK3 step on the same box."""
+"""Cost of one plane_moments(), one gradient_sums(), one transport_moments() and one three-field
+all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
+--skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out."""
 import json
 import os
 import sys
@@ -28,6 +29,24 @@ for rep in range(2):
     t0 = time.perf_counter()
     m = s.plane_moments()
     res[f"plane_moments_ms_{rep}"] = (time.perf_counter() - t0) * 1e3
+# gradient_sums: the six spectral fields read once (planes y < NY of the padded kz line stride),
+# host time of the whole call (launches, the 21 KB result copy and its synchronisation included)
+nkx, nkz = 2 * (cfg.NX // 3) + 1, (2 * cfg.NZ - 2) // 3 + 1
+nkzs = (nkz + 7) // 8 * 8 if s.spec_kzb() else nkz
+res["gradient_sums_bytes"] = 6 * cfg.NY * nkx * nkzs * 8
+for name, call in (("gradient_sums", s.gradient_sums), ("transport_moments", s.transport_moments)):
+    ts = []
+    for rep in range(5):
+        t0 = time.perf_counter()
+        r = call()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res[name + "_ms"] = ts
+    res[name + "_over_step"] = min(ts) / step_ms
+res["gradient_sums_TBps"] = res["gradient_sums_bytes"] / (min(res["gradient_sums_ms"]) * 1e-3) / 1e12
+res["gradient_sums_over_floor_5p3TBps"] = min(res["gradient_sums_ms"]) * 1e-3 / (res["gradient_sums_bytes"] / 5.3e12)
+if "--skip-fields" in sys.argv:
+    print(json.dumps(res))
+    sys.exit(0)
 t0 = time.perf_counter()
 f = s.physical_fields([192], ["u", "v", "w"])
 res["physical_fields_1plane_ms"] = (time.perf_counter() - t0) * 1e3
