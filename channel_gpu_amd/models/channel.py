@@ -113,8 +113,9 @@ class ChannelFlow:
     # ---- physical space (one rank) --------------------------------------------------------------
     def physical_fields(self, planes=None, fields=("u", "v", "w")) -> dict:
         """Physical-space planes of the current state: ``{name: ndarray (nplanes, NX, Nzp)}`` for
-        ``fields`` out of u, v, w, wx, wy, wz at the y indices ``planes`` (default: every plane).
-        The step keeps no physical field in memory; this runs the export stage on request."""
+        ``fields`` out of u, v, w, wx, wy, wz, p at the y indices ``planes`` (default: every plane).
+        The step keeps no physical field in memory; this runs the export stage on request.  ``p`` is
+        the fluctuating static pressure p' (zero plane mean), which runs the pressure solve first."""
         if planes is None:
             planes = range(self.cfg.NY)
         return self.solver.physical_fields([int(j) for j in planes], [str(f) for f in fields])
@@ -135,13 +136,26 @@ class ChannelFlow:
         one rank without a communicator, like ``plane_moments`` (which has <v^3> in row 6)."""
         return np.asarray(self.solver.transport_moments())
 
+    def pressure_hat(self) -> np.ndarray:
+        """Pi = p + |u|^2 / 2 of the current state per (kx, kz) line, ``ndarray (NY, nkx, nkz)`` complex:
+        the y-line Poisson solve with the wall condition of the v-momentum equation; zero on the mean
+        line.  One rank without a communicator; the run is not disturbed."""
+        return np.asarray(self.solver.pressure_hat())
+
+    def pressure_moments(self) -> np.ndarray:
+        """Plane means of p'p', p'u', p'v, p'w of the fluctuating static pressure
+        (``statistics.PRESSURE_ROWS``): ``ndarray (4, NY)``; one rank without a communicator."""
+        return np.asarray(self.solver.pressure_moments())
+
     # ---- time-averaged statistics -------------------------------------------------------------
-    def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False):
+    def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False,
+                          pressure: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
         ``moments``: also the third and fourth central moments (skewness / flatness profiles);
         ``budgets``: also the velocity-gradient sums and the triple products (vorticity r.m.s. and
-        the budgets of k and the Reynolds stresses; takes the plane moments too, for <v^3>)."""
+        the budgets of k and the Reynolds stresses; takes the plane moments too, for <v^3>);
+        ``pressure``: also the pressure moments (p r.m.s., <p'u'>, <p'v>, pressure diffusion)."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -157,6 +171,8 @@ class ChannelFlow:
                     self.statistics.add_moments(m)
                 if budgets:
                     self.statistics.add_budgets(self.gradient_sums(), self.transport_moments(), m[6])
+                if pressure:
+                    self.statistics.add_pressure(self.pressure_moments())
         return self.statistics
 
     def grid_points(self) -> int:

@@ -10,8 +10,9 @@ plus the scalar checks of a statistically steady Re_tau~180 channel (Re_tau, U+_
 and its y+).  Optionally it also averages the one-point central moments of the physical-space
 export (``Solver.plane_moments``) into skewness and flatness profiles of u, v, w, and the
 velocity-gradient sums (``Solver.gradient_sums``) and triple products (``Solver.transport_moments``)
-into vorticity r.m.s. profiles and the budgets of k and of the Reynolds stresses (without the
-pressure terms: the phi / omega_y formulation carries no pressure).
+into vorticity r.m.s. profiles and the budgets of k and of the Reynolds stresses, and the pressure
+moments of the y-line Poisson solve (``Solver.pressure_moments``) into the pressure r.m.s., the
+pressure-velocity correlations and the pressure-diffusion terms of those budgets.
 """
 from __future__ import annotations
 
@@ -27,6 +28,9 @@ GRADIENT_ROWS = ("wxwx", "wywy", "wzwz", "guu", "gvv", "gww", "guv")
 TRANSPORT_ROWS = ("uuv", "wwv", "uvv")
 BUDGET_STRESSES = ("k", "uu", "vv", "ww", "uv")
 BUDGET_TERMS = ("prod", "eps", "visc", "turb", "resid")
+# rows of Solver.pressure_moments(): plane means of p'p', p'u', p'v, p'w
+PRESSURE_ROWS = ("pp", "pu", "pv", "pw")
+PRESSURE_TERMS = ("pdiff_k", "pdiff_vv", "pdiff_uv")
 
 
 class TurbulenceStatistics:
@@ -50,6 +54,35 @@ class TurbulenceStatistics:
         self.grad = np.zeros((len(GRADIENT_ROWS), n))
         self.triple = np.zeros((len(TRANSPORT_ROWS), n))
         self.vvv = np.zeros(n)
+        self.npr = 0
+        self.pres = np.zeros((len(PRESSURE_ROWS), n))
+
+    def add_pressure(self, pm):
+        """One sample of the pressure moments [4, NY] (``PRESSURE_ROWS``: plane means of p'p', p'u',
+        p'v, p'w of the fluctuating static pressure)."""
+        self.pres += np.asarray(pm, float).reshape(len(PRESSURE_ROWS), self.y.size)
+        self.npr += 1
+
+    def _ops(self):
+        from ..reference.oracle import build_ops
+
+        ops = build_ops(self.y.size, self.stretch)
+        if not np.allclose(ops.y, self.y, rtol=0, atol=1e-12):
+            raise ValueError("the grid is not the tanh grid of this stretch: pass stretch= to TurbulenceStatistics")
+        return ops
+
+    def pressure_terms(self) -> dict:
+        """Unfolded pressure-diffusion terms over all NY points in solver units (``PRESSURE_TERMS``):
+        pdiff_k = -D1 <p'v>, pdiff_vv = 2 pdiff_k, pdiff_uv = -D1 <p'u'> (the uu and ww budgets have
+        none).  The pressure-strain terms are not formed directly (that needs the spectral |u|^2 / 2):
+        per component they are ``resid_s - pdiff_s`` up to the unsteadiness of the average; their
+        trace is zero, so ``closure_k = resid_k - pdiff_k`` is what is left of the k budget."""
+        if self.npr == 0:
+            raise ValueError("no pressure samples")
+        ops = self._ops()
+        pm = self.pres / self.npr
+        pk = -(ops.D1 @ pm[2])
+        return {"pdiff_k": pk, "pdiff_vv": 2.0 * pk, "pdiff_uv": -(ops.D1 @ pm[1])}
 
     def add_budgets(self, grad, triple, vvv):
         """One sample of the velocity-gradient sums [7, NY] (``GRADIENT_ROWS``), the triple products
@@ -71,16 +104,12 @@ class TurbulenceStatistics:
           turb   -D1 of (uuv + vvv + wwv) / 2, uuv, vvv, wwv, uvv
           resid  -(prod - eps + visc + turb)
 
-        ``resid`` is what closes the balance: the pressure terms (pressure diffusion and pressure
-        strain, which this formulation cannot form) plus the unsteadiness of the finite average.
+        ``resid`` is what closes the balance: the pressure terms (pressure diffusion, see
+        ``pressure_terms``, and pressure strain) plus the unsteadiness of the finite average.
         D1 and D2 are the dense compact operators of ``reference.oracle.build_ops``."""
         if self.n == 0 or self.nb == 0:
             raise ValueError("no budget samples")
-        from ..reference.oracle import build_ops
-
-        ops = build_ops(self.y.size, self.stretch)
-        if not np.allclose(ops.y, self.y, rtol=0, atol=1e-12):
-            raise ValueError("the grid is not the tanh grid of this stretch: pass stretch= to TurbulenceStatistics")
+        ops = self._ops()
         nu = self.nu
         U = self.U / self.n
         uu, vv, ww, uv = self.ms / self.n
@@ -168,6 +197,18 @@ class TurbulenceStatistics:
             sc = self.nu / ut ** 4
             for k, a in self.budgets().items():
                 out[k] = sc * fold(a, -1.0 if k.endswith("_uv") else 1.0)
+        if self.npr:
+            pm = self.pres / self.npr
+            # p' in units of u_tau^2, <p'u'> and <p'v> in u_tau^3; <p'v> is antisymmetric about the
+            # centreline (v -> -v), and so is -D1 <p'u'> like every term of the uv budget
+            out["p_rms"] = np.sqrt(np.maximum(fold(pm[0]), 0.0)) / ut ** 2
+            out["pu"] = fold(pm[1]) / ut ** 3
+            out["pv"] = fold(pm[2], -1.0) / ut ** 3
+            sc = self.nu / ut ** 4
+            for k, a in self.pressure_terms().items():
+                out[k] = sc * fold(a, -1.0 if k.endswith("_uv") else 1.0)
+            if self.nb:
+                out["closure_k"] = out["resid_k"] - out["pdiff_k"]
         return out
 
     def summary(self) -> dict:
@@ -204,6 +245,10 @@ class TurbulenceStatistics:
             names += " " + " ".join(extra)
         if self.nb:
             extra = ["wx_rms", "wy_rms", "wz_rms"] + [f"{t}_{s}" for s in BUDGET_STRESSES for t in BUDGET_TERMS]
+            cols += [p[k] for k in extra]
+            names += " " + " ".join(extra)
+        if self.npr:
+            extra = ["p_rms", "pu", "pv"] + list(PRESSURE_TERMS) + (["closure_k"] if self.nb else [])
             cols += [p[k] for k in extra]
             names += " " + " ".join(extra)
         cols = np.column_stack(cols)

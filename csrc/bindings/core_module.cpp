@@ -73,7 +73,7 @@ PYBIND11_MODULE(_core, m) {
       RW(symmetry_every) RW(checkpoint_every) RW(log_every) RW(precision) RW(decomposition) RW(pr) RW(pc) RW(seed)
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
-      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every);
+      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -303,7 +303,35 @@ PYBIND11_MODULE(_core, m) {
              std::copy(t.begin(), t.end(), a.mutable_data());
              return a;
            },
-           "plane means of u'u'v, wwv, u'vv: (3, NY) (one rank)");
+           "plane means of u'u'v, wwv, u'vv: (3, NY) (one rank)")
+      .def("pressure_hat",
+           [](Solver& s) {
+             std::vector<std::complex<double>> v;
+             {
+               py::gil_scoped_release r;
+               v = s.pressure_hat();
+             }
+             const Plan& p = s.plan();
+             py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(p.NY), static_cast<py::ssize_t>(p.nkx_loc),
+                                                  static_cast<py::ssize_t>(p.nkz_loc)});
+             std::copy(v.begin(), v.end(), a.mutable_data());
+             return a;
+           },
+           "Pi = p + |u|^2 / 2 of the current state per (kx, kz) line, (NY, nkx, nkz), zero on the mean line (one rank)")
+      .def("pressure_timing", &Solver::pressure_timing, py::call_guard<py::gil_scoped_release>(),
+           "device ms of one pressure solve: [transform stage, y-line Poisson kernel] (one rank)")
+      .def("pressure_moments",
+           [](Solver& s) {
+             std::vector<double> t;
+             {
+               py::gil_scoped_release r;
+               t = s.pressure_moments();
+             }
+             py::array_t<double> a({static_cast<py::ssize_t>(4), static_cast<py::ssize_t>(s.plan().NY)});
+             std::copy(t.begin(), t.end(), a.mutable_data());
+             return a;
+           },
+           "plane means p'p', p'u', p'v, p'w of the fluctuating static pressure: (4, NY) (one rank)");
 
   py::class_<ProcInfo>(m, "ProcInfo")
       .def(py::init<>())

@@ -227,6 +227,7 @@ Config Config::from_tree(const ConfigTree& t) {
   c.fields = t.get_string(pick(t, "fields"), c.fields);
   c.moments_every = static_cast<int>(t.get_int(pick(t, "moments_every"), c.moments_every));
   c.budget_every = static_cast<int>(t.get_int(pick(t, "budget_every"), c.budget_every));
+  c.pressure_every = static_cast<int>(t.get_int(pick(t, "pressure_every"), c.pressure_every));
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -288,6 +289,7 @@ int phys_field_index(const std::string& name) {
   static const char* kNames[6] = {"u", "v", "w", "wx", "wy", "wz"};
   for (int f = 0; f < 6; ++f)
     if (name == kNames[f]) return f;
+  if (name == "p") return kPresField;
   return -1;
 }
 
@@ -323,7 +325,7 @@ void Config::validate() const {
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
                spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
-               budget_every >= 0,
+               budget_every >= 0 && pressure_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
   CH_CHECK(rollback_cfl_factor > 0 && rollback_cfl_factor <= 1, "rollback_cfl_factor must be in (0, 1]");
@@ -332,9 +334,9 @@ void Config::validate() const {
     CH_CHECK(j >= 0 && j < NY, "spectra_planes: y index " << j << " outside [0, NY)");
   for (int j : fields_plane_list())
     CH_CHECK(j >= 0 && j < NY, "fields_planes: y index " << j << " outside [0, NY)");
-  CH_CHECK(!fields_list().empty(), "fields must name at least one of u, v, w, wx, wy, wz");
+  CH_CHECK(!fields_list().empty(), "fields must name at least one of u, v, w, wx, wy, wz, p");
   for (const std::string& f : fields_list())
-    CH_CHECK(phys_field_index(f) >= 0, "fields: unknown field '" << f << "' (u, v, w, wx, wy, wz)");
+    CH_CHECK(phys_field_index(f) >= 0, "fields: unknown field '" << f << "' (u, v, w, wx, wy, wz, p)");
 }
 
 std::string Config::to_string() const {
@@ -364,6 +366,7 @@ std::string Config::to_string() const {
   o << "  fields_every = " << fields_every << ";\n  fields_planes = \"" << fields_planes << "\";\n";
   o << "  fields = \"" << fields << "\";\n  moments_every = " << moments_every << ";\n";
   o << "  budget_every = " << budget_every << ";\n";
+  o << "  pressure_every = " << pressure_every << ";\n";
   o << "};\n";
   return o.str();
 }

@@ -452,11 +452,13 @@ void Solver::free_all() {
   h_tdt_ = nullptr;
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
                   static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
-                  static_cast<void*>(d_grad_)})
+                  static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_)})
     if (p) (void)hipFree(p);
   state_ = out_ = phys_ = xbuf_ = zbuf_ = dscal_ = snap_ = d_spec_ = d_sym_ = d_real_ = nullptr;
   d_mom_ = nullptr;
   d_grad_ = nullptr;
+  d_pres_ = nullptr;
+  d_pmom_ = nullptr;
   real_n_ = 0;
   d_rowtab_ = nullptr;
   d_y_ = nullptr;
@@ -912,7 +914,7 @@ void Solver::x_chunk(const XArgs& xa, const XSrc& src, int y0, int ny, XArgs& xc
   xc.nfields = 6;
 }
 
-void Solver::transforms(int n, bool /*stats*/) {
+void Solver::transforms(int n, bool /*stats*/, void* dst_fields) {
   const Plan& p = plan_;
   XArgs xa = x_args();
   ZArgs za;
@@ -946,10 +948,11 @@ void Solver::transforms(int n, bool /*stats*/) {
   da.Re = cfg_.Re;
   da.dy_uniform = 2.0 / (p.NY - 1);
 
+  CH_CHECK(!dst_fields || !comm_, "transforms: a destination other than the outputs is single-rank");
   if (!comm_) {
     XSrc src = x_src_local(xa);
     XDst dst;
-    dst.base = out_;
+    dst.base = dst_fields ? dst_fields : out_;
     dst.ndst = 1;
     dst.kx_start[0] = 0;
     dst.kx_start[1] = p.nkx;
@@ -988,7 +991,7 @@ void Solver::transforms(int n, bool /*stats*/) {
         zphys(zc, ph, tw_z_, fp64_, cs);
         ev(2, true, cs);
         XDst dc = dst;
-        dc.base = static_cast<char*>(out_) + so;
+        dc.base = static_cast<char*>(dst.base) + so;
         xc.nfields = 3;
         ev(3, false, cs);
         xfft_forward(xc, ph, dc, tw_x_, fp64_, cs);
@@ -2163,6 +2166,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (cfg_.fields_every > 0 && nstep_ % cfg_.fields_every == 0) write_field_files();
     if (cfg_.moments_every > 0 && nstep_ % cfg_.moments_every == 0) write_moment_files(plane_moments());
     if (cfg_.budget_every > 0 && nstep_ % cfg_.budget_every == 0) write_budget_files();
+    if (cfg_.pressure_every > 0 && nstep_ % cfg_.pressure_every == 0) write_pressure_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();
       prepare();
@@ -2375,10 +2379,15 @@ void Solver::write_spectra_files(const Spectra& sp) {
 // the blocked layout, planes past ny clamped at the loads and masked at the stores (also in the
 // plane tiles of the wide kernels), so a run of planes is transformed as it is requested.
 void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
-                           const std::function<void(int, int, const void*)>& sink, double* d_triple) {
+                           const std::function<void(int, int, const void*)>& sink, double* d_triple, bool pres,
+                           double* d_pmom) {
   CH_CHECK(!comm_, "physical-space export is single-rank: it needs a solver without a communicator");
   const Plan& p = plan_;
   if (!prepared_) prepare();
+  // pressure mode: u, v, w and Pi (field 0 of d_pres_, x-transformed into slot 3 of the scratch); the
+  // solve runs first, its transform stage uses the same scratch
+  CH_CHECK(!pres || (nf == 4 && (out_mask & 7u) == (out_mask & ~8u) && !d_triple), "export: the pressure mode takes u, v, w, p");
+  if (pres) pressure_device();
   const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
   const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
   const size_t plane = static_cast<size_t>(p.NX) * p.Nzp;
@@ -2406,8 +2415,20 @@ void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask
     XArgs xc;
     XSrc sc;
     x_chunk(xa, src, y0, ny, xc, sc);
-    if (!combine_) xc.nfields = nf;  // (the combine mode forms all six)
+    if (!combine_) xc.nfields = pres ? 3 : nf;  // (the combine mode forms all six)
     xfft_backward(xc, sc, phys_, tw_x_, fp64_, s_comp_);
+    if (pres) {
+      XArgs xp = xc;
+      xp.nfields = 1;
+      xp.combine = 0;
+      xp.zero_mean_field = -1;
+      XSrc sp;
+      sp.base = static_cast<const char*>(d_pres_) + (static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
+      sp.nsrc = 1;
+      sp.kx_start[0] = 0;
+      sp.kx_start[1] = p.nkx;
+      xfft_backward(xp, sp, static_cast<char*>(phys_) + 3 * physn_ * esz_, tw_x_, fp64_, s_comp_);
+    }
     ZRealArgs za;
     za.NX = p.NX;
     za.Nzp = p.Nzp;
@@ -2421,6 +2442,8 @@ void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask
     za.out_field_stride = static_cast<long long>(ny * plane);
     za.moments = d_mom;
     za.triple = d_triple;
+    za.pres = pres ? 1 : 0;
+    za.pmom = d_pmom;
     za.U = d_mean_;
     za.NY = p.NY;
     zreal(za, phys_, tw_z_, fp64_, s_comp_);
@@ -2433,20 +2456,59 @@ void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask
   }
 }
 
+// The export passes of a field selection (phys_field_index values): one pass of the six physical-stage
+// fields, or, with p, a pressure-mode pass (u, v, w and Pi, which takes field slot 3) that also serves
+// u, v, w, and a plain pass for any of wx, wy, wz beside it.
+namespace {
+struct ExportPass {
+  unsigned mask = 0;
+  int nf = 0;
+  bool pres = false;
+  // slot of field f (phys_field_index) among this pass's exported fields, -1 if another pass has it
+  int slot(int f) const {
+    const int bit = f == kPresField ? (pres ? 3 : -1) : ((pres && f >= 3) ? -1 : f);
+    if (bit < 0 || !((mask >> bit) & 1u)) return -1;
+    int sl = 0;
+    for (int b = 0; b < bit; ++b) sl += (mask >> b) & 1u;
+    return sl;
+  }
+};
+std::vector<ExportPass> export_passes(const std::vector<int>& fidx) {
+  bool pres = false;
+  unsigned lo = 0, hi = 0;
+  for (int f : fidx) {
+    if (f == kPresField) pres = true;
+    else if (f < 3) lo |= 1u << f;
+    else hi |= 1u << f;
+  }
+  auto top = [](unsigned m) {
+    int n = 0;
+    for (int b = 0; b < 6; ++b)
+      if ((m >> b) & 1u) n = b + 1;
+    return n;
+  };
+  std::vector<ExportPass> out;
+  if (pres) {
+    out.push_back(ExportPass{lo | 8u, 4, true});
+    if (hi) out.push_back(ExportPass{hi, top(hi), false});
+  } else {
+    out.push_back(ExportPass{lo | hi, top(lo | hi), false});
+  }
+  return out;
+}
+}  // namespace
+
 Solver::PhysFields Solver::physical_fields(const std::vector<int>& planes, const std::vector<std::string>& names) {
   CH_CHECK(!comm_, "physical_fields: the export is single-rank (a solver without a communicator)");
   const Plan& p = plan_;
   CH_CHECK(!names.empty() && !planes.empty(), "physical_fields: no fields or no planes requested");
   std::vector<int> fidx;
-  unsigned mask = 0;
-  int nf = 0;
   for (const std::string& nm : names) {
     const int f = phys_field_index(nm);
-    CH_CHECK(f >= 0, "physical_fields: unknown field '" << nm << "' (u, v, w, wx, wy, wz)");
+    CH_CHECK(f >= 0, "physical_fields: unknown field '" << nm << "' (u, v, w, wx, wy, wz, p)");
     fidx.push_back(f);
-    mask |= 1u << f;
-    nf = std::max(nf, f + 1);
   }
+  const std::vector<ExportPass> passes = export_passes(fidx);
   for (int y : planes) CH_CHECK(y >= 0 && y < p.NY, "physical_fields: plane " << y << " outside [0, NY)");
   std::vector<int> ys = planes;
   std::sort(ys.begin(), ys.end());
@@ -2461,20 +2523,27 @@ Solver::PhysFields Solver::physical_fields(const std::vector<int>& planes, const
   // positions of each plane in the request, slot of each field among the exported ones
   std::vector<std::vector<size_t>> pos(p.NY);
   for (size_t i = 0; i < np; ++i) pos[planes[i]].push_back(i);
-  int slot_of[6] = {0, 0, 0, 0, 0, 0};
-  for (int f = 0, sl = 0; f < 6; ++f)
-    if ((mask >> f) & 1u) slot_of[f] = sl++;
-  export_planes(ys, nf, mask, nullptr, [&](int y0, int ny, const void* h) {
-    for (size_t k = 0; k < names.size(); ++k)
-      for (int y = 0; y < ny; ++y) {
-        const size_t so = (static_cast<size_t>(slot_of[fidx[k]]) * ny + y) * plane;
-        for (size_t i : pos[y0 + y]) {
-          double* d = out.data.data() + (k * np + i) * plane;
-          if (fp64_) std::copy(static_cast<const double*>(h) + so, static_cast<const double*>(h) + so + plane, d);
-          else std::copy(static_cast<const float*>(h) + so, static_cast<const float*>(h) + so + plane, d);
+  for (const ExportPass& ps : passes)
+    export_planes(ys, ps.nf, ps.mask, nullptr, [&](int y0, int ny, const void* h) {
+      for (size_t k = 0; k < names.size(); ++k) {
+        const int sl = ps.slot(fidx[k]);
+        if (sl < 0) continue;
+        for (int y = 0; y < ny; ++y) {
+          const size_t so = (static_cast<size_t>(sl) * ny + y) * plane;
+          for (size_t i : pos[y0 + y]) {
+            double* d = out.data.data() + (k * np + i) * plane;
+            if (fp64_) std::copy(static_cast<const double*>(h) + so, static_cast<const double*>(h) + so + plane, d);
+            else std::copy(static_cast<const float*>(h) + so, static_cast<const float*>(h) + so + plane, d);
+            if (fidx[k] == kPresField) {  // p' = r - <r>_plane, after widening
+              double m = 0.0;
+              for (size_t q = 0; q < plane; ++q) m += d[q];
+              m /= static_cast<double>(plane);
+              for (size_t q = 0; q < plane; ++q) d[q] -= m;
+            }
+          }
         }
       }
-  });
+    }, nullptr, ps.pres);
   return out;
 }
 
@@ -2511,6 +2580,144 @@ std::vector<double> Solver::transport_moments() {
   HIP_CHECK(hipMemcpyAsync(m.data(), d_mom_ + n, nt * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
   HIP_CHECK(hipStreamSynchronize(s_comp_));
   return m;
+}
+
+// ---- pressure ------------------------------------------------------------------------------------
+// The step's transform stage (x-backward, z stage, x-forward; substep index 1: no CFL maxima, no dt
+// update) once more, from K-SPEC's outputs of the current state into d_pres_ instead of over them,
+// then the y-line Poisson solve in place over H_x.  state_ and out_ are only read: the next step sees
+// what it would have seen.  phys_ is scratch between steps, as the export assumes.
+void Solver::pressure_device(double* ms) {
+  CH_CHECK(!comm_, "pressure: the pressure solve is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  if (!prepared_) prepare();
+  if (!d_pres_) {
+    HIP_CHECK(hipMalloc(&d_pres_, 3 * spec_ * esz_));
+    HIP_CHECK(hipMemsetAsync(d_pres_, 0, 3 * spec_ * esz_, s_comp_));
+  }
+  hipEvent_t te[3] = {nullptr, nullptr, nullptr};
+  if (ms) {
+    for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(te[0], s_comp_));
+  }
+  transforms(1, false, d_pres_);
+  if (ms) HIP_CHECK(hipEventRecord(te[1], s_comp_));
+  PressureArgs a;
+  a.N = p.NY;
+  a.lines = p.nkx_loc * nkzs_;
+  a.nkz = nkzs_;
+  a.nkz_real = p.nkz_loc;
+  a.kzb = kzb_;
+  a.kz0 = p.kz0;
+  a.kx0 = p.kx0;
+  a.nkx = p.nkx;
+  a.Kx = p.Kx;
+  a.ax = p.ax;
+  a.az = p.az;
+  a.nu = 1.0 / cfg_.Re;
+  char* h = static_cast<char*>(d_pres_);
+  a.hx = h;
+  a.hy = h + spec_ * esz_;
+  a.hz = h + 2 * spec_ * esz_;
+  a.phi = field_ptr(PHI);
+  a.pi = h;
+  pressure_solve(ytab_, a, fp64_, s_comp_);
+  if (ms) {
+    HIP_CHECK(hipEventRecord(te[2], s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    float t01 = 0, t12 = 0;
+    HIP_CHECK(hipEventElapsedTime(&t01, te[0], te[1]));
+    HIP_CHECK(hipEventElapsedTime(&t12, te[1], te[2]));
+    ms[0] = t01;
+    ms[1] = t12;
+    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+  }
+}
+
+std::vector<double> Solver::pressure_timing() {
+  std::vector<double> ms(2, 0.0);
+  pressure_device(ms.data());
+  return ms;
+}
+
+std::vector<std::complex<double>> Solver::pressure_hat() {
+  pressure_device();
+  const Plan& p = plan_;
+  std::vector<std::complex<double>> t(spec_);
+  if (fp64_) {
+    std::vector<double2> h(spec_);
+    HIP_CHECK(hipMemcpyAsync(h.data(), d_pres_, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
+  } else {
+    std::vector<float2> h(spec_);
+    HIP_CHECK(hipMemcpyAsync(h.data(), d_pres_, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
+  }
+  // device layout -> canonical [y][kx][kz]; what is left behind (padded kz lines and rows of the
+  // blocked layout) must be exactly zero: the x transform of the export reads whole tiles
+  std::vector<std::complex<double>> out(canon_);
+  for (int y = 0; y < p.NY; ++y)
+    for (int i = 0; i < p.nkx_loc; ++i)
+      for (int k = 0; k < p.nkz_loc; ++k) {
+        std::complex<double>& e = t[dev_index(y, i, k)];
+        out[(static_cast<size_t>(y) * p.nkx_loc + i) * p.nkz_loc + k] = e;
+        e = 0.0;
+      }
+  size_t bad = 0;
+  for (size_t i = 0; i < spec_; ++i) bad += (t[i].real() != 0.0 || t[i].imag() != 0.0) ? 1 : 0;
+  CH_CHECK(bad == 0, "pressure: " << bad << " padding elements of the spectral layout are not zero");
+  return out;
+}
+
+std::vector<double> Solver::pressure_moments() {
+  CH_CHECK(!comm_, "pressure_moments: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const size_t N = static_cast<size_t>(p.NY), nm = kMomRows * N, np = kPresRows * N;
+  if (!d_pmom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pmom_), (nm + np) * sizeof(double)));
+  if (!prepared_) prepare();
+  HIP_CHECK(hipMemsetAsync(d_pmom_, 0, (nm + np) * sizeof(double), s_comp_));
+  std::vector<int> ys(p.NY);
+  for (int j = 0; j < p.NY; ++j) ys[j] = j;
+  // (the moments give <u'>, which is zero to rounding but is subtracted all the same, <v> and <w>
+  // are exactly the mean line's zeros)
+  export_planes(ys, 4, 0u, d_pmom_, nullptr, nullptr, true, d_pmom_ + nm);
+  std::vector<double> h(nm + np);
+  HIP_CHECK(hipMemcpyAsync(h.data(), d_pmom_, (nm + np) * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  // central moments: <p'p'> = <r^2> - <r>^2, <p'u'> = <r u'> - <r><u'>, <p'v> = <r v>, <p'w> = <r w>
+  std::vector<double> m(4 * N);
+  const double* r = h.data() + nm;
+  for (size_t j = 0; j < N; ++j) {
+    const double rm = r[j], um = h[j];
+    m[j] = r[N + j] - rm * rm;
+    m[N + j] = r[2 * N + j] - rm * um;
+    m[2 * N + j] = r[3 * N + j];
+    m[3 * N + j] = r[4 * N + j];
+  }
+  return m;
+}
+
+// one line of NY values per call and file, as write_stats_files: the pressure r.m.s. and <p'u'>, <p'v>
+void Solver::write_pressure_files() {
+  if (comm_) {
+    if (!pres_note_ && plan_.rank == 0)
+      std::fprintf(stderr, "[channel] pressure_every: PRMS.dat, PU.dat, PV.dat skipped (the pressure solve is single-rank)\n");
+    pres_note_ = true;
+    return;
+  }
+  const std::vector<double> m = pressure_moments();
+  const int N = plan_.NY;
+  auto line = [&](const char* name, const double* v, bool root) {
+    std::ofstream f(cfg_.path + name, std::ios::app);
+    f.precision(8);
+    for (int j = 0; j < N; ++j) f << " " << std::scientific << (root ? std::sqrt(std::max(0.0, v[j])) : v[j]);
+    f << " \n";
+  };
+  line("PRMS.dat", m.data(), true);
+  line("PU.dat", m.data() + N, false);
+  line("PV.dat", m.data() + 2 * N, false);
 }
 
 // ---- velocity-gradient sums -----------------------------------------------------------------------
@@ -2595,16 +2802,9 @@ void Solver::write_field_files() {
   std::vector<int> ys = planes;
   std::sort(ys.begin(), ys.end());
   ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
-  unsigned mask = 0;
-  int nf = 0;
-  for (const std::string& nm : names) {
-    const int f = phys_field_index(nm);
-    mask |= 1u << f;
-    nf = std::max(nf, f + 1);
-  }
-  int slot_of[6] = {0, 0, 0, 0, 0, 0};
-  for (int f = 0, sl = 0; f < 6; ++f)
-    if ((mask >> f) & 1u) slot_of[f] = sl++;
+  std::vector<int> fidx;
+  for (const std::string& nm : names) fidx.push_back(phys_field_index(nm));
+  const std::vector<ExportPass> passes = export_passes(fidx);
   char step[16];
   std::snprintf(step, sizeof(step), "%08ld", nstep_);
   const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
@@ -2630,16 +2830,38 @@ void Solver::write_field_files() {
   const std::streamoff data0 = static_cast<std::streamoff>(10 + hlen);
   std::vector<std::vector<size_t>> pos(p.NY);
   for (size_t i = 0; i < planes.size(); ++i) pos[planes[i]].push_back(i);
-  export_planes(ys, nf, mask, nullptr, [&](int y0, int ny, const void* h) {
-    for (size_t k = 0; k < names.size(); ++k)
-      for (int y = 0; y < ny; ++y) {
-        const size_t so = (static_cast<size_t>(slot_of[phys_field_index(names[k])]) * ny + y) * plane * tsz;
-        for (size_t i : pos[y0 + y]) {
-          files[k].seekp(data0 + static_cast<std::streamoff>(i * plane * tsz));
-          files[k].write(static_cast<const char*>(h) + so, static_cast<std::streamsize>(plane * tsz));
+  std::vector<char> pbuf;
+  for (const ExportPass& ps : passes)
+    export_planes(ys, ps.nf, ps.mask, nullptr, [&](int y0, int ny, const void* h) {
+      for (size_t k = 0; k < names.size(); ++k) {
+        const int sl = ps.slot(fidx[k]);
+        if (sl < 0) continue;
+        for (int y = 0; y < ny; ++y) {
+          const size_t so = (static_cast<size_t>(sl) * ny + y) * plane * tsz;
+          const char* src = static_cast<const char*>(h) + so;
+          if (fidx[k] == kPresField) {  // p' = r - <r>_plane (the mean formed in double)
+            pbuf.assign(src, src + plane * tsz);
+            double m = 0.0;
+            if (fp64_) {
+              double* q = reinterpret_cast<double*>(pbuf.data());
+              for (size_t e = 0; e < plane; ++e) m += q[e];
+              m /= static_cast<double>(plane);
+              for (size_t e = 0; e < plane; ++e) q[e] -= m;
+            } else {
+              float* q = reinterpret_cast<float*>(pbuf.data());
+              for (size_t e = 0; e < plane; ++e) m += q[e];
+              m /= static_cast<double>(plane);
+              for (size_t e = 0; e < plane; ++e) q[e] = static_cast<float>(q[e] - m);
+            }
+            src = pbuf.data();
+          }
+          for (size_t i : pos[y0 + y]) {
+            files[k].seekp(data0 + static_cast<std::streamoff>(i * plane * tsz));
+            files[k].write(src, static_cast<std::streamsize>(plane * tsz));
+          }
         }
       }
-  });
+    }, nullptr, ps.pres);
   for (size_t k = 0; k < names.size(); ++k) {
     files[k].close();
     CH_CHECK(!files[k].fail(), "writing the field file of '" << names[k] << "' failed");

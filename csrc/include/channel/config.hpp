@@ -88,9 +88,10 @@ struct Config {
   // Physical-space export (one rank; the step itself keeps no physical field in memory).
   int fields_every = 0;                // 0 = off; FIELD_<name>_<step>.npy planes + FIELDS_<step>.json
   std::string fields_planes = "";      // comma-separated y indices ("" = every plane)
-  std::string fields = "u,v,w";        // of u, v, w, wx, wy, wz
+  std::string fields = "u,v,w";        // of u, v, w, wx, wy, wz, p (the fluctuating static pressure)
   int budget_every = 0;                // 0 = off; vorticity r.m.s., dissipation and triple-product profiles (W?RMS.dat, EPS_*.dat, TRIPLE_*.dat)
   int moments_every = 0;               // 0 = off; skewness / flatness profiles of u, v, w (*SKEW.dat, *FLAT.dat)
+  int pressure_every = 0;              // 0 = off; pressure r.m.s. and pressure-velocity profiles (PRMS.dat, PU.dat, PV.dat; one rank)
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});
@@ -107,7 +108,9 @@ struct Config {
 // FFT lengths the transform kernels are instantiated for: 2^k (16..2048) and 3, 5, 7, 9, 11, 13, 15 x 2^k
 // (2^k >= 16, at most 2048 points)
 bool fft_length_supported(int n);
-// index of a physical-stage field name (u v w wx wy wz) or -1
+// index of a physical-stage field name (u v w wx wy wz) or -1; "p" (the fluctuating static pressure,
+// formed by the export stage from the pressure solve) is kPresField
+constexpr int kPresField = 6;
 int phys_field_index(const std::string& name);
 
 }  // namespace channel

@@ -132,6 +132,28 @@ void kspec_launch(const YTablesDev& t, const SpecArgs& a, bool fp64, hipStream_t
 // split (CHANNEL_KSPEC_SPLIT=1) reads "kspec_kernel<..., 1, 1> + kspec_out_kernel<R, T, W, XM>" (tests)
 std::string kspec_last_variant();
 
+// ---- pressure (y-line Poisson solve, outside the step) ---------------------------------------
+// Per line with k2 > 0: (K - k2 M) Pi = M S on the interior rows, S = i al Hx + i be Hz + D1 Hy, and
+// (D1 Pi)(+-1) = Hy(+-1) + nu phi(+-1) at the walls, solved as Pi = Pi_p + c1 g1 + c2 g2 with the
+// Dirichlet Helmholtz factorisation (right-hand sides M S, e_0, e_N) and the 2 x 2 system of the
+// dense D1's wall rows (pressure.hip).  Pi = p + |u|^2 / 2; the mean line, padded kz lines (local kz
+// >= nkz_real) and rows >= N of the blocked layout are written as zero.  pi may be hx (in place).
+struct PressureArgs {
+  int N = 0;              // NY
+  int lines = 0;          // local lines = nkx_loc * nkz, line = ikx_local * nkz + kz
+  int nkz = 0, nkz_real = 0, kx0 = 0, nkx = 0, Kx = 0;  // nkz = kz line stride (kzb: padded to 8)
+  int kzb = 0;            // spectral layout (spec_index)
+  int kz0 = 0;
+  double ax = 1, az = 2;  // 2 pi / LX, 2 pi / LZ
+  double nu = 1.0 / 3250.0;
+  const void* hx = nullptr;   // H = u x omega (what the step's transform stage writes)
+  const void* hy = nullptr;
+  const void* hz = nullptr;
+  const void* phi = nullptr;  // the state (its two wall rows are read)
+  void* pi = nullptr;
+};
+void pressure_solve(const YTablesDev& t, const PressureArgs& a, bool fp64, hipStream_t stream);
+
 // ---- FFT stages ---------------------------------------------------------------------------
 // Per-pass FFT twiddle tables for length n (FftPlan T1/T2 layout, fft_device.hpp), fp32 or fp64.
 struct Twiddles {
@@ -267,8 +289,16 @@ struct ZRealArgs {
   // u'u'v, w w v, u'v v accumulated (+=) into triple[kTripleRows][NY].  The second pair is then
   // transformed as (w, v) instead of (w, 0), so w and v meet in the same registers.
   double* triple = nullptr;
+  // pressure mode (optional; nfields == 4, field 3 = Pi' = p + |u|^2 / 2 without its plane mean, U set,
+  // no triple): the second pair is (w, Pi') and r = Pi' - U u' - (u'^2 + v^2 + w^2) / 2, the static
+  // pressure up to its plane mean, is formed per point from the u', v kept from the first pair; bit 3 of
+  // out_mask exports r in the place of field 3, and pmom (optional) accumulates (+=) the plane means of
+  // r, r^2, r u', r v, r w into pmom[kPresRows][NY] (products in double)
+  int pres = 0;
+  double* pmom = nullptr;
 };
 constexpr int kTripleRows = 3;  // u'u'v, wwv, u'vv
+constexpr int kPresRows = 5;    // r, r^2, r u', r v, r w
 void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
 
 // standalone FFT entry points for tests: batched C2C along the contiguous axis

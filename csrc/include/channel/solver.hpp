@@ -137,6 +137,17 @@ class Solver {
   // plane means of u'u'v, wwv, u'vv, [kTripleRows][NY] (one rank without a communicator, through the
   // export stage like plane_moments)
   std::vector<double> transport_moments();
+  // Pressure of the current state (one rank without a communicator; kernels.hpp PressureArgs):
+  // Pi = p + |u|^2 / 2 per (kx, kz) line in the canonical [y][kx][kz] layout, zero on the mean line.
+  // The step's transform stage runs once more into a buffer of its own (d_pres_), so neither the
+  // state nor K-SPEC's outputs are written and the next step is unchanged bitwise.
+  std::vector<std::complex<double>> pressure_hat();
+  // plane means <p'p'>, <p'u'>, <p'v>, <p'w> of the fluctuating static pressure p' (central moments),
+  // [4][NY], through the export stage (kernels.hpp ZRealArgs::pres)
+  std::vector<double> pressure_moments();
+  // device time in ms of one pressure solve without the host copy of pressure_hat: [the transform
+  // stage, the y-line Poisson kernel] (events on the compute stream; tools/export_cost.py)
+  std::vector<double> pressure_timing();
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -179,7 +190,8 @@ class Solver {
   void choose_layout();
   void alloc();
   void free_all();
-  void transforms(int substep, bool stats);
+  // dst (one rank without a communicator): where the x-forward writes H_x, H_y, H_z (default out_)
+  void transforms(int substep, bool stats, void* dst = nullptr);
   void kspec(int mode, int substep, bool stats);
   void a2a_spec(const void* spec, void* xb, bool to_phys);
   void a2a_rows(void* xexp, void* zrows, bool to_z);
@@ -206,6 +218,9 @@ class Solver {
   void write_field_files();
   void write_moment_files(const std::vector<double>& m);
   void write_budget_files();
+  void write_pressure_files();
+  // Pi of the current state into field 0 of d_pres_ (device part of pressure_hat)
+  void pressure_device(double* ms = nullptr);
   // x-backward arguments of the whole local slab (transforms and the export): the common part, the
   // one-rank source (sets the blocked layout in xa) and the arguments of planes [y0, y0 + ny)
   XArgs x_args() const;
@@ -215,7 +230,8 @@ class Solver {
   // 0 .. nf-1 are transformed, those of out_mask handed to sink(y0, ny, host [slot][ny][NX][Nzp]
   // in the storage precision), the moments accumulated into d_mom (either may be absent)
   void export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
-                     const std::function<void(int, int, const void*)>& sink, double* d_triple = nullptr);
+                     const std::function<void(int, int, const void*)>& sink, double* d_triple = nullptr,
+                     bool pres = false, double* d_pmom = nullptr);
   void write_json(const StepLog& L, double ms_per_step);
   void wait(hipStream_t s);           // stream sync with the communicator watchdog (P > 1)
   void invalidate_graphs();
@@ -363,6 +379,9 @@ class Solver {
   double* d_mom_ = nullptr;  // export: [kMomRows][NY], then [kTripleRows][NY]
   double* d_grad_ = nullptr;  // gradient sums: [kGradRows][NY]
   bool budget_note_ = false;  // the "triple files skipped" note has been printed
+  void* d_pres_ = nullptr;    // pressure: three spectral fields (H, then Pi over H_x), lazily allocated
+  double* d_pmom_ = nullptr;  // pressure: [kMomRows][NY] (dropped), then [kPresRows][NY]
+  bool pres_note_ = false;    // the "pressure files skipped" note has been printed
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 
   bool use_graph_ = true;

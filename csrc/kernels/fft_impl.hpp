@@ -1864,11 +1864,14 @@ inline int ztpr_env() {
 // With ZRealArgs::triple the second pair is (w, v) instead of (w, 0) and the mixed triple products
 // u'u'v, u'vv (first pair) and wwv (second pair) are summed beside the moments, from the same
 // registers and through the same reduction.
+// PRES (ZRealArgs::pres, an instantiation of its own: the others are unchanged by it): the second pair
+// is (w, Pi'); the first pair's u, v stay in registers and r = Pi' - U u' - (u'^2 + v^2 + w^2) / 2 is
+// formed per point in double, stored in the place of field 3 and summed as r, r^2, r u', r v, r w.
 template <typename T>
 struct alignas(16) RVec {
   T v[16 / sizeof(T)];
 };
-template <int NZP, typename T>
+template <int NZP, typename T, bool PRES = false>
 __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(T))))
     zreal_kernel(ZRealArgs a, const typename C2<T>::type* fields, const typename C2<T>::type* tw) {
   using T2 = typename C2<T>::type;
@@ -1886,9 +1889,13 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
   __shared__ T2 tws[TS];
   constexpr int kAccRows = kMomRows + kTripleRows;  // per plane: the moments, then the triple products
   __shared__ double acc[MAXP * kAccRows];
+  __shared__ double pacc[PRES ? MAXP * kPresRows : 1];
   const int tid = threadIdx.x, t = tid % TPR, w = tid / TPR;
   for (int i = tid; i < TS; i += NT) tws[i] = tw[i];
   for (int i = tid; i < MAXP * kAccRows; i += NT) acc[i] = 0.0;
+  if constexpr (PRES)
+    for (int i = tid; i < MAXP * kPresRows; i += NT) pacc[i] = 0.0;
+  RVec<T> ku[PRES ? EV : 1], kv[PRES ? EV : 1];  // PRES: u, v of the first pair
   __syncthreads();
   T2* row = s + w * PITCH;
   T2* frow = s + (tid / TPRF) * RWW * PITCH;  // first row of this thread's transform group
@@ -1901,7 +1908,7 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
   const bool rv = r < nrows;
   const long long rc = rv ? r : nrows - 1;
   const int yl = static_cast<int>(rc / a.NX), pl0 = static_cast<int>(rfirst / a.NX);
-  const double Uy = a.moments ? a.U[a.y0 + yl] : 0.0;
+  const double Uy = (PRES || a.moments) ? a.U[a.y0 + yl] : 0.0;
   const int npairs = (a.nfields + 1) / 2;
   for (int p = 0; p < npairs; ++p) {
     const bool tv = a.triple && p == 1;  // triple products: w pairs with v (the host checks nfields == 3)
@@ -1934,6 +1941,7 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
     const bool mom = a.moments && p < 2;
     double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double tr[2] = {0, 0};  // (u, v): u'u'v, u'vv; (w, v): wwv
+    double pm[kPresRows] = {0, 0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < EV; ++i) {
       const int nv = t + TPR * i;
@@ -1944,6 +1952,27 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
           const T2 z = row[fft_pidx(nv * VEC + j)];
           ra.v[j] = z.x;
           rb.v[j] = z.y;
+        }
+        if constexpr (PRES) {
+          if (p == 0) {
+            ku[i] = ra;
+            kv[i] = rb;
+          } else if (p == 1) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+              const double du = static_cast<double>(ku[i].v[j]) - Uy, dv = static_cast<double>(kv[i].v[j]);
+              const double dw = static_cast<double>(ra.v[j]);
+              const double rr = static_cast<double>(rb.v[j]) - Uy * du - 0.5 * (du * du + dv * dv + dw * dw);
+              rb.v[j] = static_cast<T>(rr);
+              if (rv) {
+                pm[0] += rr;
+                pm[1] += rr * rr;
+                pm[2] += rr * du;
+                pm[3] += rr * dv;
+                pm[4] += rr * dw;
+              }
+            }
+          }
         }
         if (rv) {
           if (wa) *reinterpret_cast<RVec<T>*>(oa + nv * VEC) = ra;
@@ -2004,7 +2033,29 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
         }
       }
     }
+    if constexpr (PRES) {
+      if (p == 1 && a.pmom) {  // (block-uniform)
+#pragma unroll
+        for (int q = 0; q < kPresRows; ++q) {
+          double v = pm[q];
+#pragma unroll
+          for (int o = (TPR < 64 ? TPR : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+          if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&pacc[(yl - pl0) * kPresRows + q], v);
+        }
+      }
+    }
     row_sync<TPRF>();  // this pair's LDS reads precede the next pair's writes
+  }
+  if constexpr (PRES) {
+    if (a.pmom) {
+      __syncthreads();
+      const int pl1 = static_cast<int>(min(nrows - 1, rfirst + ZWT - 1) / a.NX);
+      const double sc = 1.0 / (static_cast<double>(a.NX) * NZP);
+      for (int i = tid; i < MAXP * kPresRows; i += NT) {
+        const int pl = pl0 + i / kPresRows, q = i % kPresRows;
+        if (pl <= pl1) atomicAdd(&a.pmom[q * a.NY + a.y0 + pl], pacc[i] * sc);
+      }
+    }
   }
   if (a.moments) {
     __syncthreads();
@@ -2027,8 +2078,12 @@ static void zreal_launch(const ZRealArgs& a, const void* fields, const Twiddles&
   const long long nrows = static_cast<long long>(a.ny) * a.NX;
   const long long ngroups = (nrows + ZR - 1) / ZR;
   CH_CHECK(ngroups < (1LL << 31), "zreal: too many rows for one launch");
-  hipLaunchKernelGGL((zreal_kernel<NN, T>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
-                     static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
+  if (a.pres)
+    hipLaunchKernelGGL((zreal_kernel<NN, T, true>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
+                       static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
+  else
+    hipLaunchKernelGGL((zreal_kernel<NN, T>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
+                       static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
 }
 
 // ---- standalone batched C2C (tests) ----------------------------------------------------------

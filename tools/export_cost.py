@@ -1,5 +1,6 @@
-"""Cost of one plane_moments(), one gradient_sums(), one transport_moments() and one three-field
-all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
+"""Cost of one plane_moments(), one gradient_sums(), one transport_moments(), one pressure solve (the
+device part of pressure_hat()), one pressure_moments() and one three-field all-plane physical_fields()
+at 1024x385x1024 fp32, relative to one RK3 step in the same process.
 --skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out."""
 import json
 import os
@@ -44,6 +45,23 @@ for name, call in (("gradient_sums", s.gradient_sums), ("transport_moments", s.t
     res[name + "_over_step"] = min(ts) / step_ms
 res["gradient_sums_TBps"] = res["gradient_sums_bytes"] / (min(res["gradient_sums_ms"]) * 1e-3) / 1e12
 res["gradient_sums_over_floor_5p3TBps"] = min(res["gradient_sums_ms"]) * 1e-3 / (res["gradient_sums_bytes"] / 5.3e12)
+# pressure: device time of the transform stage and of the y-line Poisson kernel (hipEvents), the
+# kernel against its streaming floor of four field passes (three reads, one write) at 5.3 TB/s
+res["pressure_solve_bytes"] = 4 * cfg.NY * nkx * nkzs * 8
+tt = [s.pressure_timing() for _ in range(5)]
+res["pressure_transforms_ms"] = [t[0] for t in tt]
+res["pressure_solve_ms"] = [t[1] for t in tt]
+res["pressure_hat_device_ms"] = min(t[0] + t[1] for t in tt)
+res["pressure_hat_device_over_step"] = res["pressure_hat_device_ms"] / step_ms
+res["pressure_solve_floor_over_time_5p3TBps"] = (res["pressure_solve_bytes"] / 5.3e12) / (min(res["pressure_solve_ms"]) * 1e-3)
+ts = []
+for rep in range(5):
+    t0 = time.perf_counter()
+    pm = s.pressure_moments()
+    ts.append((time.perf_counter() - t0) * 1e3)
+res["pressure_moments_ms"] = ts
+res["pressure_moments_over_step"] = min(ts) / step_ms
+res["p_rms_centre"] = float(pm[0, 192] ** 0.5)
 if "--skip-fields" in sys.argv:
     print(json.dumps(res))
     sys.exit(0)
