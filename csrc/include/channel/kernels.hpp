@@ -262,6 +262,9 @@ struct ZArgs {
   float* maxima = nullptr;           // [4]: |u|max, |v|max, |w|max, cfl sum max (atomicMax)
   int lds_poison = 0;                // debug: fill the LDS with NaN before use
 };
+// template arguments of this thread's last zphys_kernel launch, in rocprofv3's kernel-name form (the
+// last argument: pair 1 of the next row staged in the per-wave LDS slot; tests)
+std::string zphys_last_variant();
 // physical-space stage: 6 fields (u,v,w,wx,wy,wz) [y][x][kz] -> z C2R -> H = u x omega -> z R2C
 // -> truncated H_x,H_y,H_z written in place over fields 0..2.
 void zphys(const ZArgs& a, void* fields, const Twiddles& tw, bool fp64, hipStream_t s);

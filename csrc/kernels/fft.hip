@@ -25,6 +25,18 @@ static std::string xfft_variant_string(const XVariant& v) {
   return s + ">";
 }
 
+ZVariant& zphys_variant_slot() {
+  static thread_local ZVariant v;
+  return v;
+}
+std::string zphys_last_variant() {
+  const ZVariant& v = zphys_variant_slot();
+  auto b = [](bool x) { return x ? "true" : "false"; };
+  return std::string("zphys_kernel<") + std::to_string(v.nn) + ", " + (v.f64 ? "double" : "float") + ", " + b(v.seg) + ", " +
+         b(v.zh) + ", " + std::to_string(v.tpr) + ", " + std::to_string(v.zr) + ", " + std::to_string(v.wpe) + ", " +
+         std::to_string(v.zf) + ", " + b(v.dma) + ">";
+}
+
 void Twiddles::build(int n_, bool fp64_) {
   release();
   n = n_;
@@ -174,6 +186,7 @@ static void build_reg_twiddles(int n, bool fp64, void** out) {
 void zphys(const ZArgs& a_in, void* fields, const Twiddles& tw, bool fp64, hipStream_t s) {
   ZArgs a = a_in;
   a.diag = fft_diag();
+  if (lds_poison_enabled()) a.lds_poison = 1;  // (callers outside the solver: the tensor entry point)
   if (a.nseg <= 1) {
     a.nseg = 1;
     a.kz_start[0] = 0;

@@ -1045,7 +1045,7 @@ constexpr int zphys_rows() {
 }
 
 template <int NZP, typename T, bool SEG, bool ZH = true, int TPRT = zphys_tpr<NZP>(sizeof(T)),
-          int ZWT = zphys_rows<NZP, T, TPRT>(), int WPE = 2, int ZF = 3>
+          int ZWT = zphys_rows<NZP, T, TPRT>(), int WPE = 2, int ZF = 3, bool DMA = false>
 __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu(WPE), target("no-load-store-opt"))) zphys_kernel(ZArgs a, typename C2<T>::type* fields,
                                                          const typename C2<T>::type* tw) {
   using T2 = typename C2<T>::type;
@@ -1079,9 +1079,29 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
   // real H_z: half-length complex transform + post twiddles (HalfPlan) where one exists
   using Hp = HalfPlan<NZP>;
   constexpr bool kHalf = ZH && Hp::ok;
-  constexpr int TSA = TS + ((kHalf || kR4) ? Hp::SIZE : 0) + (kR4 ? kR4TwSize : 0);
+  // kR4Hz: all five transforms of a row go through fft1024_4x16x16, which reads only its own tables
+  // (tw3), so only those are staged (8,160 B instead of 24,352 B: the three-pass plan's and the half
+  // plan's tables were copied by every block and never read)
+  constexpr int TW0 = kR4Hz ? TS + Hp::SIZE : 0;  // first staged entry of the global table
+  constexpr int TSA = kR4Hz ? kR4TwSize : TS + ((kHalf || kR4) ? Hp::SIZE : 0) + (kR4 ? kR4TwSize : 0);
   __shared__ T2 tws[TSA];  // twiddles staged once per block: LDS latency instead of L2 in the passes
   __shared__ float red[4][NWB];
+  // one-wave-per-row fp32 rows without segments: the row's field pairs are prefetched (below)
+  constexpr bool kPrefetch = sizeof(T) == 4 && NZP <= 1024 && !SEG;
+  // DMA: pair 1 (w, omega_x) of the wave's NEXT row waits in a per-wave LDS slot, filled a whole row
+  // ahead by asynchronous global->LDS copies (buffer_load_dwordx4 ... lds: no VGPR destination, so
+  // the prefetch depth no longer costs registers).  The slot is the row's global image (field 2's nkz
+  // elements, then field 3's): lane t reads its elements t + 64 i back with contiguous ds_read_b64.
+  // An array of its own: the compiler then orders only the slot's reads behind the copies' vmcnt,
+  // not the transforms' row-buffer and table reads.
+  constexpr bool kDma = DMA && kR4Hz && kPrefetch && TPRT == 64;
+  static_assert(!DMA || kDma, "zphys: the LDS slot variant is the 1024-point fp32 one-segment kernel at ZF >= 3");
+  constexpr int kSlotF = NZP / 3 + 1;                  // elements per field in the slot (= nkz)
+  constexpr int kSlotPieces = kSlotF * 8 / 16;         // 16-byte pieces per field
+  // (a slot ends with a pad that takes the unmasked tail of the last copy instruction: slot_issue)
+  constexpr int kSlotStride = 2 * kSlotF + 2 * (64 * ((kSlotPieces + 63) / 64) - kSlotPieces);
+  static_assert(!kDma || (kSlotF % 2 == 0 && sizeof(T2) == 8), "zphys: slot rows must be whole 16-byte pieces");
+  __shared__ __attribute__((aligned(16))) T2 zslot[kDma ? NWB * kSlotStride : 1];
   // lane: wave lane (reductions); t: thread within the row; w: row within the block
   const int tid = threadIdx.x, lane = tid & 63;
   int t = tid % TPR, w = tid / TPR;
@@ -1089,9 +1109,10 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
     lds_poison_fill(s, sizeof(s));
     lds_poison_fill(tws, sizeof(tws));
     lds_poison_fill(red, sizeof(red));
+    if constexpr (kDma) lds_poison_fill(zslot, sizeof(zslot));
     __syncthreads();
   }
-  for (int i = tid; i < TSA; i += ZWT * TPR) tws[i] = tw[i];
+  for (int i = tid; i < TSA; i += ZWT * TPR) tws[i] = tw[TW0 + i];
   __syncthreads();
   T2* row = s + w * PITCH;
   T2* frow = s + (tid / TPRF) * RWW * PITCH;  // first row of this thread's transform group
@@ -1131,8 +1152,11 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
         const unsigned o = (rb + static_cast<unsigned>(min(k, nkz - 1))) * static_cast<unsigned>(sizeof(T2));
         const T2 x = *reinterpret_cast<const T2*>(reinterpret_cast<const char*>(A) + o);
         const T2 y = *reinterpret_cast<const T2*>(reinterpret_cast<const char*>(B) + o);
-        va[i] = ld ? x : T2{0, 0};
-        vb[i] = ld ? y : T2{0, 0};
+        // (the register-edge rows mask k >= nkz where they consume the pair, and all their rows are
+        // valid: no select here -- under the `more` branch of the next row's pair 0 it was emitted
+        // at the loads, a vmcnt wait for 8 of the 12 right after their issue)
+        va[i] = kRegEdge || ld ? x : T2{0, 0};
+        vb[i] = kRegEdge || ld ? y : T2{0, 0};
       }
     } else {
 #pragma unroll
@@ -1160,7 +1184,6 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
   // NEXT row's first pair is loaded during this row's forward transforms, so no row starts on an
   // exposed load latency (the one-shot launch exposed it once per row: with the
   // transforms skipped the stage still took 55 of its 88 us per 8-plane chunk).
-  constexpr bool kPrefetch = sizeof(T) == 4 && NZP <= 1024 && !SEG;
   T2 pa[kPrefetch ? MK : 1], pb[kPrefetch ? MK : 1];
   // the middle pass's twiddles in registers (fp32 register-edge rows: 30 VGPRs against 15 LDS reads
   // per transform; only in the CHANNEL_ZFFT=1 plan -- ZFFT=0 keeps the LDS reads, A/B)
@@ -1169,16 +1192,79 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
   if constexpr (kMidReg) middle_twiddles<NZP>(tws, twm, lane);
   // 4 x 16 x 16: the second pass's twiddles W_64^(k2 r), k2 = lane / 16, in registers; the third
   // pass's W_1024^(lane r) are read from the LDS table
-  const T2* tw3 = tws + TS + Hp::SIZE;  // (Twiddles::build: after the half plan's tables at n = 1024)
+  const T2* tw3 = tws + (TS + Hp::SIZE - TW0);  // (Twiddles::build: after the half plan's tables at n = 1024)
   if constexpr (kR4) {
 #pragma unroll
     for (int r = 1; r < 16; ++r) twm[r - 1] = tw3[kR4Tw2 + (r - 1) * 4 + lane / 16];
   }
-  // (not kept: a second buffer issuing pair 2 two transforms ahead and the next row's pair 1 a
-  // row ahead: 28 spilled VGPRs, 39.4 vs 37.7 ms/step, profiles/r03s3/ab_zphys_prefetch2.txt)
+  // (not kept: a second REGISTER buffer issuing pair 2 two transforms ahead and the next row's pair
+  // 1 a row ahead: 28 spilled VGPRs, 39.4 vs 37.7 ms/step, profiles/r03s3/ab_zphys_prefetch2.txt;
+  // kDma has that schedule with the LDS slot in the place of the second buffer)
+  // kDma: the asynchronous copy of pair 1 of row rr into the wave's slot: per field 171 16-byte
+  // pieces = 3 wave instructions (the LDS destination of a lane is the wave-uniform base + 16 lane;
+  // rows are whole pieces: the launcher checks the alignment).  In the buffer form (buffer_load ...
+  // lds, one descriptor per field, 32-bit byte offsets): after a global_load_lds the compiler
+  // turns every later wait of the wave into vmcnt(0) / lgkmcnt(0) (it books a FLAT instruction
+  // that touches both memories as unordered), which drained the copies at pair 2's wait, one
+  // transform after their issue, and un-counted the transforms' LDS waits.
+  // The third instruction of a field has 43 pieces left; its lanes 43..63 are not masked off (a
+  // masked instruction is a branch the compiler cannot count through, see below) but copy something
+  // harmless: field 2's write on into the start of field 3's image and copy exactly the pieces
+  // that belong there (field 3 of the same row lies field_stride further: the launcher checks that
+  // the offset fits 32 bits), field 3's copy the row's last piece into the pad behind the slot.
+  // live = false: six dummy copies of one in-bounds piece (this row's first; one cache line per
+  // instruction) into the slot nobody reads again, instead of a branch around the copies: the count
+  // of copies in flight is then the same on every path, and the compiler's wait for pair 2 (issued
+  // BEFORE them; vmcnt retires in order) is the counted vmcnt(6) that leaves them in flight.  With
+  // the copies under a branch that wait is vmcnt(0).
+  auto slot_issue = [&](long long rr, bool live, int ww, int ln) {
+    if constexpr (kDma) {
+      constexpr int NI = (kSlotPieces + 63) / 64, TAIL = kSlotPieces - 64 * (NI - 1);
+      const unsigned rb = static_cast<unsigned>(rr) * static_cast<unsigned>(kSlotF) * static_cast<unsigned>(sizeof(T2));
+      const unsigned fsb = static_cast<unsigned>(fs) * static_cast<unsigned>(sizeof(T2));
+      T2* const sl = zslot + __builtin_amdgcn_readfirstlane(ww) * kSlotStride;
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        // (2^32 - 1 records: no range check; the casts spell the builtin's parameter types, which the
+        // host pass wants exact, or it drops the kernel's stub without a diagnostic)
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<void*>(fields + (2 + f) * fs), static_cast<short>(0),
+                                                          static_cast<int>(-1), 0x00020000);
+        char* dst = reinterpret_cast<char*>(sl + f * kSlotF);
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+          unsigned o = rb + static_cast<unsigned>(1024 * j + 16 * ln);
+          if (j == NI - 1) {
+            const unsigned over = f ? rb + 16u * (kSlotPieces - 1) : fsb + rb + 16u * static_cast<unsigned>(ln - TAIL);
+            o = ln < TAIL ? o : over;
+          }
+          o = live ? o : rb;
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + 1024 * j), 16,
+                                                   static_cast<int>(o), 0, 0, 0);
+        }
+      }
+    }
+  };
+  // ... and the read of the lane's elements t + 64 i of both fields out of it (as fetch: a clamped
+  // index, zeros selected afterwards).  The compiler waits for the copies (vmcnt) before these reads.
+  auto slot_read = [&](int ww, int tt, T2 (&va)[MK], T2 (&vb)[MK]) {
+    if constexpr (kDma) {
+      const T2* sl = zslot + ww * kSlotStride;
+#pragma unroll
+      for (int i = 0; i < MK; ++i) {
+        const int k = tt + TPR * i;
+        const int kc = min(k, kSlotF - 1);
+        const T2 x = sl[kc], y = sl[kSlotF + kc];
+        va[i] = k < kSlotF ? x : T2{0, 0};
+        vb[i] = k < kSlotF ? y : T2{0, 0};
+      }
+    }
+  };
   long long g = blockIdx.x;
   if constexpr (kPrefetch) {
-    if (g < ngroups) fetch(g * ZWT + w, 0, pa, pb);
+    if (g < ngroups) {
+      fetch(g * ZWT + w, 0, pa, pb);
+      slot_issue(g * ZWT + w, true, w, t);  // the first row has no predecessor: its pair 1 goes out here
+    }
   }
   // kPairHz: H_z of the wave's previous row, waiting for its partner (wave-uniform state), parked
   // in a per-wave LDS area (slot pair i / 2 of lane l at (i / 2) * 64 + l: conflict-free b64
@@ -1227,7 +1313,24 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
       T2 va[MK], vb[MK];
-      if constexpr (kPrefetch) {
+      if constexpr (kDma) {
+        // pair 1 out of the slot; the reads are back (lgkmcnt) before the next row's copies are
+        // issued into it, which then have three transforms and the stores to land (the wait for the
+        // next row's pair 0, issued after them, retires them).  The slot is the wave's own: no
+        // block barrier.  The last row issues dummy copies (slot_issue)
+        if (p == 1) {
+          slot_read(w, t, va, vb);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+          slot_issue(more ? rnext : r, more, w, t);
+        } else {
+#pragma unroll
+          for (int i = 0; i < MK; ++i) {
+            va[i] = pa[i];
+            vb[i] = pb[i];
+          }
+        }
+      } else if constexpr (kPrefetch) {
 #pragma unroll
         for (int i = 0; i < MK; ++i) {
           va[i] = pa[i];
@@ -1252,7 +1355,10 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
           d[i] = ok ? (k == 0 ? T2{va[i].x, vb[i].x} : T2{va[i].x - vb[i].y, va[i].y + vb[i].x}) : T2{0, 0};
           m[i] = ok && k > 0 ? T2{va[i].x + vb[i].y, vb[i].x - va[i].y} : T2{0, 0};
         }
-        if constexpr (kPrefetch) {
+        if constexpr (kDma) {
+          // pair 1 never passes through pa / pb, so pair 2 goes out two transforms ahead
+          if (p == 0) fetch(r, 2, pa, pb);
+        } else if constexpr (kPrefetch) {
           if (p < 2) fetch(r, p + 1, pa, pb);
         }
         const int src = (64 - t) & 63;
@@ -1805,6 +1911,36 @@ inline bool zpers_enabled() {
   return on;
 }
 
+// CHANNEL_ZDMA=1: the 1024-point fp32 z stage stages pair 1 of a wave's next row in a per-wave LDS
+// slot (zphys_kernel DMA) instead of the register-only prefetch of its field pairs (A/B; 0 or unset:
+// off).  Not the default: on the headline grid, parent and slot alternating four times each, the
+// medians were 30.79-31.90 against 31.01-31.32 ms/step, and the z kernel alone gained less than
+// the two chunk streams trade among their co-running kernels (profiles/zdma/README.md)
+inline bool zdma_enabled() {
+  static const bool on = [] {
+    const char* e = std::getenv("CHANNEL_ZDMA");
+    return e && std::atoi(e) != 0;
+  }();
+  return on;
+}
+// the slot's 16-byte copies need every row of every field to start at a 16-byte boundary: nkz even
+// (rows start at multiples of nkz), the field stride even and the base aligned; and a row's byte
+// offset plus one field stride fits 32 bits (zphys_kernel slot_issue reaches into the next field)
+inline bool zdma_ok(const ZArgs& a, const void* fields) {
+  const unsigned long long rows = static_cast<unsigned long long>(a.ny) * a.NX;
+  return a.nkz % 2 == 0 && a.field_stride % 2 == 0 && reinterpret_cast<uintptr_t>(fields) % 16 == 0 &&
+         a.field_stride > 0 && (static_cast<unsigned long long>(a.field_stride) + rows * a.nkz) * 8 < (1ull << 32) && zdma_enabled();
+}
+
+// The template arguments of this thread's last z-stage launch, as in the rocprofv3 kernel names
+// ("zphys_kernel<1024, float, false, true, 64, 4, 2, 3, true>"; the last one: the LDS slot variant),
+// recorded like xfft_note_variant and formatted only when asked for (zphys_last_variant)
+struct ZVariant {
+  int nn = 0, tpr = 0, zr = 0, wpe = 0, zf = 0;
+  bool f64 = false, seg = false, zh = false, dma = false;
+};
+ZVariant& zphys_variant_slot();
+
 template <int NN, typename T, int TPR, int WPE = 2>
 static void zphys_launch_tpr(const ZArgs& a, void* fields, const Twiddles& tw, hipStream_t s, bool zh) {
   using T2 = typename C2<T>::type;
@@ -1815,13 +1951,21 @@ static void zphys_launch_tpr(const ZArgs& a, void* fields, const Twiddles& tw, h
                    static_cast<unsigned long long>(nrows) * a.nkz * sizeof(T2) >= (1ull << 32);
   auto kern = seg ? (zh ? zphys_kernel<NN, T, true, true, TPR, ZR, WPE> : zphys_kernel<NN, T, true, false, TPR, ZR, WPE>)
                   : (zh ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE> : zphys_kernel<NN, T, false, false, TPR, ZR, WPE>);
+  int zfv = 3;
+  bool dma = false;
   if constexpr (sizeof(T) == 4 && NN == 1024 && TPR == 64 && WPE == 2) {
     const int zf = zfft_mode();
     if (!seg && zh && zf == 0) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 0>;
     if (!seg && zh && zf == 1) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 1>;
     if (!seg && zh && zf == 2) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 2>;
     if (!seg && zh && zf == 4) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4>;
+    if (!seg && zh && zf >= 0 && zf <= 4 && zf != 3) zfv = zf;
+    // ZF >= 3: pair 1 of the next row through the per-wave LDS slot where the rows are whole
+    // 16-byte pieces; the register-only prefetch otherwise
+    dma = !seg && zh && zfv >= 3 && zdma_ok(a, fields);
+    if (dma) kern = zfv == 4 ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 3, true>;
   }
+  zphys_variant_slot() = ZVariant{NN, TPR, ZR, WPE, zfv, sizeof(T) == 8, seg, zh, dma};
   const long long ngroups = (nrows + ZR - 1) / ZR;
   const long long cap = zpers_enabled() ? persist_blocks(reinterpret_cast<const void*>(kern), ZR * TPR, "CHANNEL_Z_BPC") : ngroups;
   dim3 grid(static_cast<unsigned>(std::min(ngroups, cap)));
