@@ -147,15 +147,30 @@ class ChannelFlow:
         (``statistics.PRESSURE_ROWS``): ``ndarray (4, NY)``; one rank without a communicator."""
         return np.asarray(self.solver.pressure_moments())
 
+    def static_pressure_hat(self) -> np.ndarray:
+        """The fluctuating static pressure p' of the current state in spectral space, truncated to the
+        retained modes: ``ndarray (NY, nkx, nkz)`` complex, zero on the mean line.  The pressure-mode
+        export pass with the return trip of p' to spectral space; one rank without a communicator,
+        the run is not disturbed."""
+        return np.asarray(self.solver.static_pressure_hat())
+
+    def pressure_strain(self) -> np.ndarray:
+        """Parseval plane sums of p' with the strain factors (``statistics.PSTRAIN_ROWS``): the
+        pressure-strain terms of the uu, vv, ww, uv budgets, <p'u'>, <p'v> and the retained-band part
+        of <p'p'>: ``ndarray (7, NY)``; one rank without a communicator."""
+        return np.asarray(self.solver.pressure_strain())
+
     # ---- time-averaged statistics -------------------------------------------------------------
     def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False,
-                          pressure: bool = False):
+                          pressure: bool = False, pressure_strain: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
         ``moments``: also the third and fourth central moments (skewness / flatness profiles);
         ``budgets``: also the velocity-gradient sums and the triple products (vorticity r.m.s. and
         the budgets of k and the Reynolds stresses; takes the plane moments too, for <v^3>);
-        ``pressure``: also the pressure moments (p r.m.s., <p'u'>, <p'v>, pressure diffusion)."""
+        ``pressure``: also the pressure moments (p r.m.s., <p'u'>, <p'v>, pressure diffusion);
+        ``pressure_strain``: also the pressure-strain terms (with ``budgets`` and ``pressure`` the
+        per-component budgets then close: ``closure_uu``, ``closure_vv``, ``closure_ww``, ``closure_uv``)."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -173,6 +188,8 @@ class ChannelFlow:
                     self.statistics.add_budgets(self.gradient_sums(), self.transport_moments(), m[6])
                 if pressure:
                     self.statistics.add_pressure(self.pressure_moments())
+                if pressure_strain:
+                    self.statistics.add_pressure_strain(self.pressure_strain())
         return self.statistics
 
     def grid_points(self) -> int:

@@ -12,7 +12,9 @@ export (``Solver.plane_moments``) into skewness and flatness profiles of u, v, w
 velocity-gradient sums (``Solver.gradient_sums``) and triple products (``Solver.transport_moments``)
 into vorticity r.m.s. profiles and the budgets of k and of the Reynolds stresses, and the pressure
 moments of the y-line Poisson solve (``Solver.pressure_moments``) into the pressure r.m.s., the
-pressure-velocity correlations and the pressure-diffusion terms of those budgets.
+pressure-velocity correlations and the pressure-diffusion terms of those budgets, and the Parseval
+sums of the spectral static pressure (``Solver.pressure_strain``) into the pressure-strain terms, with
+which the uu, vv, ww and uv budgets close component by component.
 """
 from __future__ import annotations
 
@@ -31,6 +33,10 @@ BUDGET_TERMS = ("prod", "eps", "visc", "turb", "resid")
 # rows of Solver.pressure_moments(): plane means of p'p', p'u', p'v, p'w
 PRESSURE_ROWS = ("pp", "pu", "pv", "pw")
 PRESSURE_TERMS = ("pdiff_k", "pdiff_vv", "pdiff_uv")
+# rows of Solver.pressure_strain(): 2 <p' du'/dx>, 2 <p' dv/dy>, 2 <p' dw/dz>, <p' (du'/dy + dv/dx)>,
+# <p'u'>, <p'v> and the retained-band part of <p'p'>
+PSTRAIN_ROWS = ("ps_uu", "ps_vv", "ps_ww", "ps_uv", "pu", "pv", "pp_band")
+PSTRAIN_TERMS = ("pstrain_uu", "pstrain_vv", "pstrain_ww", "pstrain_uv")
 
 
 class TurbulenceStatistics:
@@ -56,6 +62,22 @@ class TurbulenceStatistics:
         self.vvv = np.zeros(n)
         self.npr = 0
         self.pres = np.zeros((len(PRESSURE_ROWS), n))
+        self.nps = 0
+        self.pstr = np.zeros((len(PSTRAIN_ROWS), n))
+
+    def add_pressure_strain(self, ps):
+        """One sample of the pressure-strain sums [7, NY] (``PSTRAIN_ROWS``)."""
+        self.pstr += np.asarray(ps, float).reshape(len(PSTRAIN_ROWS), self.y.size)
+        self.nps += 1
+
+    def pressure_strain_terms(self) -> dict:
+        """Unfolded pressure-strain terms over all NY points in solver units (``PSTRAIN_TERMS``):
+        pstrain_uu = 2 <p' du'/dx>, pstrain_vv = 2 <p' dv/dy>, pstrain_ww = 2 <p' dw/dz> (their sum is
+        zero: continuity) and pstrain_uv = <p' (du'/dy + dv/dx)>."""
+        if self.nps == 0:
+            raise ValueError("no pressure-strain samples")
+        ps = self.pstr / self.nps
+        return {name: ps[q] for q, name in enumerate(PSTRAIN_TERMS)}
 
     def add_pressure(self, pm):
         """One sample of the pressure moments [4, NY] (``PRESSURE_ROWS``: plane means of p'p', p'u',
@@ -74,9 +96,9 @@ class TurbulenceStatistics:
     def pressure_terms(self) -> dict:
         """Unfolded pressure-diffusion terms over all NY points in solver units (``PRESSURE_TERMS``):
         pdiff_k = -D1 <p'v>, pdiff_vv = 2 pdiff_k, pdiff_uv = -D1 <p'u'> (the uu and ww budgets have
-        none).  The pressure-strain terms are not formed directly (that needs the spectral |u|^2 / 2):
-        per component they are ``resid_s - pdiff_s`` up to the unsteadiness of the average; their
-        trace is zero, so ``closure_k = resid_k - pdiff_k`` is what is left of the k budget."""
+        none).  The pressure-strain terms are those of ``pressure_strain_terms``; their trace is zero,
+        so ``closure_k = resid_k - pdiff_k`` is what is left of the k budget, and per component
+        ``closure_s = resid_s - pdiff_s - pstrain_s``: the unsteadiness of the finite average."""
         if self.npr == 0:
             raise ValueError("no pressure samples")
         ops = self._ops()
@@ -209,6 +231,16 @@ class TurbulenceStatistics:
                 out[k] = sc * fold(a, -1.0 if k.endswith("_uv") else 1.0)
             if self.nb:
                 out["closure_k"] = out["resid_k"] - out["pdiff_k"]
+        if self.nps:
+            # pressure strain in units of u_tau^4 / nu, folded like the other terms of its budget
+            sc = self.nu / ut ** 4
+            for k, a in self.pressure_strain_terms().items():
+                out[k] = sc * fold(a, -1.0 if k.endswith("_uv") else 1.0)
+            if self.nb and self.npr:
+                out["closure_uu"] = out["resid_uu"] - out["pstrain_uu"]
+                out["closure_ww"] = out["resid_ww"] - out["pstrain_ww"]
+                out["closure_vv"] = out["resid_vv"] - out["pdiff_vv"] - out["pstrain_vv"]
+                out["closure_uv"] = out["resid_uv"] - out["pdiff_uv"] - out["pstrain_uv"]
         return out
 
     def summary(self) -> dict:
@@ -249,6 +281,12 @@ class TurbulenceStatistics:
             names += " " + " ".join(extra)
         if self.npr:
             extra = ["p_rms", "pu", "pv"] + list(PRESSURE_TERMS) + (["closure_k"] if self.nb else [])
+            cols += [p[k] for k in extra]
+            names += " " + " ".join(extra)
+        if self.nps:
+            extra = list(PSTRAIN_TERMS)
+            if self.nb and self.npr:
+                extra += ["closure_uu", "closure_vv", "closure_ww", "closure_uv"]
             cols += [p[k] for k in extra]
             names += " " + " ".join(extra)
         cols = np.column_stack(cols)

@@ -86,6 +86,40 @@ def pressure_moments(o: OracleSolver, Pi: np.ndarray) -> np.ndarray:
     return np.stack([(p * q).mean(axis=(1, 2)) for q in (p, u, v, w)])
 
 
+PSTRAIN_ROWS = ("ps_uu", "ps_vv", "ps_ww", "ps_uv", "pu", "pv", "pp_band")
+
+
+def static_pressure_hat(o: OracleSolver, Pi: np.ndarray) -> np.ndarray:
+    """p-hat' [NY, nkx, nkz]: the fluctuating static pressure back in spectral space, truncated to the
+    retained modes, the mean line zero."""
+    from .oracle import phys_to_spec_full
+
+    p_hat = phys_to_spec_full(pressure_physical(o, Pi), o.plan)
+    if o.mean_line is not None:
+        p_hat[:, 0, 0] = 0
+    return p_hat
+
+
+def pressure_strain(o: OracleSolver, p_hat: np.ndarray) -> np.ndarray:
+    """[7, NY] Parseval plane sums of p-hat' with the strain factors (``PSTRAIN_ROWS``; the weights and
+    the wall-normal derivatives of ``budgets``): ps_uu = 2 <p' du'/dx>, ps_vv = 2 <p' dv/dy>,
+    ps_ww = 2 <p' dw/dz>, ps_uv = <p' (du'/dy + dv/dx)>, <p'u'>, <p'v> and the retained-band part of
+    <p'p'>.  The strain factors are band-limited to the retained modes, so the truncation of p' loses
+    nothing in rows 0 to 5."""
+    from .budgets import plane_weights, wall_normal_derivatives
+
+    p = np.asarray(p_hat, complex).reshape(o.ops.N, -1)
+    u, v, w = (o.lines(f) for f in o.fields[:3])
+    du, dv, _ = wall_normal_derivatives(o)
+    al, be = o.al, o.be
+    dot = lambda a, b: a.real * b.real + a.imag * b.imag  # noqa: E731
+    rows = [2.0 * dot(p, 1j * al * u), 2.0 * dot(p, dv), 2.0 * dot(p, 1j * be * w), dot(p, du + 1j * al * v),
+            dot(p, u), dot(p, v), dot(p, p)]
+    wgt = plane_weights(o)
+    keep = wgt > 0
+    return np.stack([r[:, keep] @ wgt[keep] for r in rows])
+
+
 def momentum_residual(o: OracleSolver, Pi: np.ndarray, o_after: OracleSolver, dt: float):
     """(q1 - q0) / dt - (H - grad Pi + nu (D2 - k2) q0) for q = u, v, w as three [NY, lines] arrays:
     q0 the prepared fields of ``o``, q1 those of ``o_after`` (``o`` advanced over ``dt``).  Zeros for

@@ -73,7 +73,8 @@ PYBIND11_MODULE(_core, m) {
       RW(symmetry_every) RW(checkpoint_every) RW(log_every) RW(precision) RW(decomposition) RW(pr) RW(pc) RW(seed)
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
-      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every);
+      RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every)
+      RW(pstrain_every);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -331,7 +332,33 @@ PYBIND11_MODULE(_core, m) {
              std::copy(t.begin(), t.end(), a.mutable_data());
              return a;
            },
-           "plane means p'p', p'u', p'v, p'w of the fluctuating static pressure: (4, NY) (one rank)");
+           "plane means p'p', p'u', p'v, p'w of the fluctuating static pressure: (4, NY) (one rank)")
+      .def("static_pressure_hat",
+           [](Solver& s) {
+             std::vector<std::complex<double>> v;
+             {
+               py::gil_scoped_release r;
+               v = s.static_pressure_hat();
+             }
+             const Plan& p = s.plan();
+             py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(p.NY), static_cast<py::ssize_t>(p.nkx_loc),
+                                                  static_cast<py::ssize_t>(p.nkz_loc)});
+             std::copy(v.begin(), v.end(), a.mutable_data());
+             return a;
+           },
+           "the fluctuating static pressure p' per (kx, kz) line, (NY, nkx, nkz), zero on the mean line (one rank)")
+      .def("pressure_strain",
+           [](Solver& s) {
+             std::vector<double> t;
+             {
+               py::gil_scoped_release r;
+               t = s.pressure_strain();
+             }
+             py::array_t<double> a({static_cast<py::ssize_t>(kPStrainRows), static_cast<py::ssize_t>(s.plan().NY)});
+             std::copy(t.begin(), t.end(), a.mutable_data());
+             return a;
+           },
+           "Parseval plane sums ps_uu, ps_vv, ps_ww, ps_uv, pu, pv, pp_band of p' with the strain factors: (7, NY) (one rank)");
 
   py::class_<ProcInfo>(m, "ProcInfo")
       .def(py::init<>())

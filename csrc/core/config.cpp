@@ -228,6 +228,7 @@ Config Config::from_tree(const ConfigTree& t) {
   c.moments_every = static_cast<int>(t.get_int(pick(t, "moments_every"), c.moments_every));
   c.budget_every = static_cast<int>(t.get_int(pick(t, "budget_every"), c.budget_every));
   c.pressure_every = static_cast<int>(t.get_int(pick(t, "pressure_every"), c.pressure_every));
+  c.pstrain_every = static_cast<int>(t.get_int(pick(t, "pstrain_every"), c.pstrain_every));
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -325,7 +326,7 @@ void Config::validate() const {
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
                spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
-               budget_every >= 0 && pressure_every >= 0,
+               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
   CH_CHECK(rollback_cfl_factor > 0 && rollback_cfl_factor <= 1, "rollback_cfl_factor must be in (0, 1]");
@@ -367,6 +368,7 @@ std::string Config::to_string() const {
   o << "  fields = \"" << fields << "\";\n  moments_every = " << moments_every << ";\n";
   o << "  budget_every = " << budget_every << ";\n";
   o << "  pressure_every = " << pressure_every << ";\n";
+  o << "  pstrain_every = " << pstrain_every << ";\n";
   o << "};\n";
   return o.str();
 }

@@ -452,8 +452,9 @@ void Solver::free_all() {
   h_tdt_ = nullptr;
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
                   static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
-                  static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_)})
+                  static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_)})
     if (p) (void)hipFree(p);
+  d_pstr_ = nullptr;
   state_ = out_ = phys_ = xbuf_ = zbuf_ = dscal_ = snap_ = d_spec_ = d_sym_ = d_real_ = nullptr;
   d_mom_ = nullptr;
   d_grad_ = nullptr;
@@ -2167,6 +2168,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (cfg_.moments_every > 0 && nstep_ % cfg_.moments_every == 0) write_moment_files(plane_moments());
     if (cfg_.budget_every > 0 && nstep_ % cfg_.budget_every == 0) write_budget_files();
     if (cfg_.pressure_every > 0 && nstep_ % cfg_.pressure_every == 0) write_pressure_files();
+    if (cfg_.pstrain_every > 0 && nstep_ % cfg_.pstrain_every == 0) write_pstrain_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();
       prepare();
@@ -2642,16 +2644,21 @@ std::vector<double> Solver::pressure_timing() {
 
 std::vector<std::complex<double>> Solver::pressure_hat() {
   pressure_device();
+  return spec_to_canonical(d_pres_, "pressure");
+}
+
+// one spectral field on the device (one rank) as canonical [y][kx][kz] complex128 on the host
+std::vector<std::complex<double>> Solver::spec_to_canonical(const void* d_field, const char* what) {
   const Plan& p = plan_;
   std::vector<std::complex<double>> t(spec_);
   if (fp64_) {
     std::vector<double2> h(spec_);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d_pres_, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipMemcpyAsync(h.data(), d_field, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
   } else {
     std::vector<float2> h(spec_);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d_pres_, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipMemcpyAsync(h.data(), d_field, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
   }
@@ -2667,7 +2674,7 @@ std::vector<std::complex<double>> Solver::pressure_hat() {
       }
   size_t bad = 0;
   for (size_t i = 0; i < spec_; ++i) bad += (t[i].real() != 0.0 || t[i].imag() != 0.0) ? 1 : 0;
-  CH_CHECK(bad == 0, "pressure: " << bad << " padding elements of the spectral layout are not zero");
+  CH_CHECK(bad == 0, what << ": " << bad << " padding elements of the spectral layout are not zero");
   return out;
 }
 
@@ -2718,6 +2725,124 @@ void Solver::write_pressure_files() {
   line("PRMS.dat", m.data(), true);
   line("PU.dat", m.data() + N, false);
   line("PV.dat", m.data() + 2 * N, false);
+}
+
+// ---- spectral static pressure, pressure-strain -------------------------------------------------------
+// The pressure-mode export pass over every plane with the return trip of r (kernels.hpp
+// ZRealArgs::spec_out): per chunk the x-backward of u, v, w and of Pi (into slot 3 of the scratch), the
+// z kernel, which leaves r-hat(x, kz) in slot 3, and the forward x transform of that one field into
+// the chunk's planes of field 1 of d_pres_ (the H_y slot, free after the solve; Pi stays in field 0).
+// The mean line, which holds <r>, is zeroed; the padding of the blocked layout is never written and
+// stays the zeros of the allocation.  Like the export it writes nothing the next step reads.
+void Solver::static_pressure_device() {
+  CH_CHECK(!comm_, "static_pressure: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  pressure_device();
+  const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
+  XArgs xa = x_args();
+  const XSrc src = x_src_local(xa);
+  char* slot3 = static_cast<char*>(phys_) + 3 * physn_ * esz_;
+  char* phat = static_cast<char*>(d_pres_) + spec_ * esz_;
+  for (int y0 = 0; y0 < p.NY; y0 += cap) {
+    const int ny = std::min(cap, p.NY - y0);
+    XArgs xc;
+    XSrc sc;
+    x_chunk(xa, src, y0, ny, xc, sc);
+    if (!combine_) xc.nfields = 3;  // (the combine mode forms all six)
+    xfft_backward(xc, sc, phys_, tw_x_, fp64_, s_comp_);
+    XArgs xp = xc;
+    xp.nfields = 1;
+    xp.combine = 0;
+    xp.zero_mean_field = -1;
+    XSrc sp;
+    const size_t so = static_cast<size_t>(static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
+    sp.base = static_cast<const char*>(d_pres_) + so;
+    sp.nsrc = 1;
+    sp.kx_start[0] = 0;
+    sp.kx_start[1] = p.nkx;
+    xfft_backward(xp, sp, slot3, tw_x_, fp64_, s_comp_);
+    ZRealArgs za;
+    za.NX = p.NX;
+    za.Nzp = p.Nzp;
+    za.nkz = p.nkz;
+    za.ny = ny;
+    za.y0 = y0;
+    za.nfields = 4;
+    za.field_stride = static_cast<long long>(physn_);
+    za.pres = 1;
+    za.spec_out = slot3;
+    za.U = d_mean_;
+    za.NY = p.NY;
+    zreal(za, phys_, tw_z_, fp64_, s_comp_);
+    // (the chunk's planes of the destination, as transforms() addresses them)
+    XDst dc;
+    dc.base = phat + so;
+    dc.ndst = 1;
+    dc.kx_start[0] = 0;
+    dc.kx_start[1] = p.nkx;
+    xfft_forward(xp, slot3, dc, tw_x_, fp64_, s_comp_);
+  }
+  zero_mean_line(phat, p.NY, kzb_, p.nkx_loc * nkzs_, fp64_, s_comp_);
+}
+
+std::vector<std::complex<double>> Solver::static_pressure_hat() {
+  static_pressure_device();
+  return spec_to_canonical(static_cast<const char*>(d_pres_) + spec_ * esz_, "static pressure");
+}
+
+std::vector<double> Solver::pressure_strain() {
+  CH_CHECK(!comm_, "pressure_strain: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const size_t n = static_cast<size_t>(kPStrainRows) * p.NY;
+  if (!d_pstr_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pstr_), n * sizeof(double)));
+  static_pressure_device();
+  HIP_CHECK(hipMemsetAsync(d_pstr_, 0, n * sizeof(double), s_comp_));
+  PStrainArgs a;
+  a.p = static_cast<const char*>(d_pres_) + spec_ * esz_;
+  if (combine_) {
+    for (int f = 0; f < kCmbIn; ++f) a.f[f] = in_field(f);
+  } else {
+    static const int kSix[4] = {0, 1, 2, 5};  // u, v, w, omega_z
+    for (int f = 0; f < 4; ++f) a.f[f] = in_field(kSix[f]);
+  }
+  a.combine = combine_ ? 1 : 0;
+  a.ax = p.ax;
+  a.az = p.az;
+  a.N = p.NY;
+  a.nkx_loc = p.nkx_loc;
+  a.kx0 = p.kx0;
+  a.nkz_loc = p.nkz_loc;
+  a.kz0 = p.kz0;
+  a.nkzs = nkzs_;
+  a.kzb = kzb_;
+  a.nkx = p.nkx;
+  a.Kx = p.Kx;
+  a.sums = d_pstr_;
+  pstrain_accumulate(a, fp64_, s_comp_);
+  std::vector<double> g(n);
+  HIP_CHECK(hipMemcpyAsync(g.data(), d_pstr_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  return g;
+}
+
+// one line of NY values per call and file, as write_stats_files: the pressure-strain terms of the uu,
+// vv, ww, uv budgets
+void Solver::write_pstrain_files() {
+  if (comm_) {
+    if (!pstr_note_ && plan_.rank == 0)
+      std::fprintf(stderr, "[channel] pstrain_every: PS_UU.dat, PS_VV.dat, PS_WW.dat, PS_UV.dat skipped (the export is single-rank)\n");
+    pstr_note_ = true;
+    return;
+  }
+  const std::vector<double> m = pressure_strain();
+  const int N = plan_.NY;
+  const char* names[4] = {"PS_UU.dat", "PS_VV.dat", "PS_WW.dat", "PS_UV.dat"};
+  for (int q = 0; q < 4; ++q) {
+    std::ofstream f(cfg_.path + names[q], std::ios::app);
+    f.precision(8);
+    for (int j = 0; j < N; ++j) f << " " << std::scientific << m[static_cast<size_t>(q) * N + j];
+    f << " \n";
+  }
 }
 
 // ---- velocity-gradient sums -----------------------------------------------------------------------

@@ -92,6 +92,7 @@ struct Config {
   int budget_every = 0;                // 0 = off; vorticity r.m.s., dissipation and triple-product profiles (W?RMS.dat, EPS_*.dat, TRIPLE_*.dat)
   int moments_every = 0;               // 0 = off; skewness / flatness profiles of u, v, w (*SKEW.dat, *FLAT.dat)
   int pressure_every = 0;              // 0 = off; pressure r.m.s. and pressure-velocity profiles (PRMS.dat, PU.dat, PV.dat; one rank)
+  int pstrain_every = 0;               // 0 = off; pressure-strain profiles of the uu, vv, ww, uv budgets (PS_*.dat; one rank)
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});

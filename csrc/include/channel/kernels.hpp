@@ -299,6 +299,11 @@ struct ZRealArgs {
   // r, r^2, r u', r v, r w into pmom[kPresRows][NY] (products in double)
   int pres = 0;
   double* pmom = nullptr;
+  // return trip of r (optional; with pres, an instantiation of its own): r goes back into the row's
+  // LDS slots as (r, 0), is forward transformed and its retained kz (k < nkz), scaled by 1 / (NX Nzp),
+  // are stored as complex [row][kz] at spec_out, x-expanded like the inputs (what xfft_forward reads).
+  // spec_out may be the place of field 3: a row's Pi is loaded before its r is stored.
+  void* spec_out = nullptr;
 };
 constexpr int kTripleRows = 3;  // u'u'v, wwv, u'vv
 constexpr int kPresRows = 5;    // r, r^2, r u', r v, r w
@@ -373,6 +378,30 @@ struct GradSumArgs {
   double* sums = nullptr;             // [kGradRows][N]
 };
 void gradsum_accumulate(const GradSumArgs& a, bool fp64, hipStream_t s);
+// Pressure-strain plane sums: the Parseval products of the spectral fluctuating static pressure p with
+// the strain factors of the current state, read once like the gradient sums (same walk, weights and
+// masks: kz = 0 once, kz > 0 twice, the mean line and the padded lines skipped; products and sums in
+// double) and accumulated (+=) into sums[kPStrainRows][N].  The wall-normal derivatives are the
+// solver's own: D u = i al v - omega_z, D v = -i (al u + be w).  Rows:
+//   ps_uu = 2 Re<p (i al u)*>, ps_vv = 2 Re<p (D v)*>, ps_ww = 2 Re<p (i be w)*>,
+//   ps_uv = Re<p (D u + i al v)*>, pu = Re<p u*>, pv = Re<p v*>, pp_band = <|p|^2>.
+constexpr int kPStrainRows = 7;
+struct PStrainArgs {
+  const void* p = nullptr;            // p-hat, in the layout of the fields
+  // six-output mode: u, v, w, omega_z (f[4] unused); combine mode: D1 v, v, D1 omega, omega, phi, from
+  // which u, w, omega_z are formed per element
+  const void* f[5] = {};
+  int combine = 0;
+  double ax = 1.0, az = 2.0;
+  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
+  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
+  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
+  int nkx = 0, Kx = 0;                // global retained kx count
+  double* sums = nullptr;             // [kPStrainRows][N]
+};
+void pstrain_accumulate(const PStrainArgs& a, bool fp64, hipStream_t s);
+// element (local kx 0, kz 0) of every plane y < N of one spectral field (lines = nkx_loc * nkzs) := 0
+void zero_mean_line(void* q, int N, int kzb, int lines, bool fp64, hipStream_t s);
 // fault injection (tests): element `elem` of a complex field becomes NaN
 void inject_nan(void* field, size_t elem, bool fp64, hipStream_t s);
 

@@ -148,6 +148,15 @@ class Solver {
   // device time in ms of one pressure solve without the host copy of pressure_hat: [the transform
   // stage, the y-line Poisson kernel] (events on the compute stream; tools/export_cost.py)
   std::vector<double> pressure_timing();
+  // The fluctuating static pressure p' of the current state in spectral space, truncated to the retained
+  // modes: canonical [y][kx][kz], zero on the mean line (one rank without a communicator).  The
+  // pressure-mode export pass over every plane with the return trip of r = p' + <r> to spectral space
+  // (kernels.hpp ZRealArgs::spec_out) into field 1 of d_pres_; nothing the next step reads is written.
+  std::vector<std::complex<double>> static_pressure_hat();
+  // Parseval plane sums of p-hat' with the strain factors, [kPStrainRows][NY] (kernels.hpp PStrainArgs:
+  // the pressure-strain terms of the uu, vv, ww, uv budgets, <p'u'>, <p'v> and the retained-band part
+  // of <p'p'>); one rank without a communicator
+  std::vector<double> pressure_strain();
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -221,6 +230,11 @@ class Solver {
   void write_pressure_files();
   // Pi of the current state into field 0 of d_pres_ (device part of pressure_hat)
   void pressure_device(double* ms = nullptr);
+  void write_pstrain_files();
+  // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat)
+  void static_pressure_device();
+  // one device spectral field as canonical [y][kx][kz]; refuses non-zero padding of the device layout
+  std::vector<std::complex<double>> spec_to_canonical(const void* d_field, const char* what);
   // x-backward arguments of the whole local slab (transforms and the export): the common part, the
   // one-rank source (sets the blocked layout in xa) and the arguments of planes [y0, y0 + ny)
   XArgs x_args() const;
@@ -379,9 +393,11 @@ class Solver {
   double* d_mom_ = nullptr;  // export: [kMomRows][NY], then [kTripleRows][NY]
   double* d_grad_ = nullptr;  // gradient sums: [kGradRows][NY]
   bool budget_note_ = false;  // the "triple files skipped" note has been printed
-  void* d_pres_ = nullptr;    // pressure: three spectral fields (H, then Pi over H_x), lazily allocated
+  void* d_pres_ = nullptr;    // pressure: three spectral fields (H, then Pi over H_x, p-hat' over H_y), lazily allocated
   double* d_pmom_ = nullptr;  // pressure: [kMomRows][NY] (dropped), then [kPresRows][NY]
   bool pres_note_ = false;    // the "pressure files skipped" note has been printed
+  double* d_pstr_ = nullptr;  // pressure strain: [kPStrainRows][NY]
+  bool pstr_note_ = false;    // the "pressure-strain files skipped" note has been printed
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 
   bool use_graph_ = true;

@@ -236,7 +236,8 @@ void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64
   CH_CHECK(!a.pres || (a.nfields == 4 && a.U && !a.triple && a.y0 >= 0 && a.y0 + a.ny <= a.NY),
            "zreal: the pressure mode takes u, v, w, Pi and U(y), without the triple products");
   CH_CHECK(!a.pmom || a.pres, "zreal: the pressure sums need the pressure mode");
-  if (a.ny == 0 || (!a.out && !a.moments && !a.pmom)) return;
+  CH_CHECK(!a.spec_out || a.pres, "zreal: the return trip to spectral space needs the pressure mode");
+  if (a.ny == 0 || (!a.out && !a.moments && !a.pmom && !a.spec_out)) return;
   CH_DISPATCH_N(a.Nzp, fft_zr_len<NN>(a, fields, tw, fp64, s));
   HIP_LAUNCH_CHECK(s);
 }

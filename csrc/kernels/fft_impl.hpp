@@ -2011,13 +2011,18 @@ inline int ztpr_env() {
 // PRES (ZRealArgs::pres, an instantiation of its own: the others are unchanged by it): the second pair
 // is (w, Pi'); the first pair's u, v stay in registers and r = Pi' - U u' - (u'^2 + v^2 + w^2) / 2 is
 // formed per point in double, stored in the place of field 3 and summed as r, r^2, r u', r v, r w.
+// SPEC (ZRealArgs::spec_out, with PRES, again an instantiation of its own): the return trip of r.  Each
+// thread writes (r, 0) back into the LDS slots it has just read, the row is forward transformed in
+// place and its retained kz, scaled by 1 / (NX Nzp), go to the x-expanded [row][kz] destination (the
+// forward x transform's input).  Rows past the end transform what the zeros left and store nothing.
 template <typename T>
 struct alignas(16) RVec {
   T v[16 / sizeof(T)];
 };
-template <int NZP, typename T, bool PRES = false>
+template <int NZP, typename T, bool PRES = false, bool SPEC = false>
 __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(T))))
     zreal_kernel(ZRealArgs a, const typename C2<T>::type* fields, const typename C2<T>::type* tw) {
+  static_assert(!SPEC || PRES, "the return trip is the pressure mode's");
   using T2 = typename C2<T>::type;
   constexpr int TPR = zphys_tpr<NZP>(sizeof(T)), ZWT = zphys_rows<NZP, T, TPR>(), NT = ZWT * TPR;
   constexpr int PITCH = FftPitch<NZP>::value;
@@ -2108,6 +2113,7 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
               const double dw = static_cast<double>(ra.v[j]);
               const double rr = static_cast<double>(rb.v[j]) - Uy * du - 0.5 * (du * du + dv * dv + dw * dw);
               rb.v[j] = static_cast<T>(rr);
+              if constexpr (SPEC) row[fft_pidx(nv * VEC + j)] = T2{rb.v[j], T(0)};
               if (rv) {
                 pm[0] += rr;
                 pm[1] += rr * rr;
@@ -2187,6 +2193,22 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
           if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&pacc[(yl - pl0) * kPresRows + q], v);
         }
       }
+      if constexpr (SPEC) {
+        if (p == 1) {  // (block-uniform: the host checks nfields == 4)
+          row_sync<TPRF>();  // the row's (r, 0) are in place
+          wave_fft<NZP, RWW, PITCH, false, TPRF>(frow, tws, ft);
+          const T sc = static_cast<T>(1.0 / (static_cast<double>(a.NX) * NZP));
+          T2* O = static_cast<T2*>(a.spec_out) + rc * nkz;
+#pragma unroll
+          for (int i = 0; i < MK; ++i) {
+            const int k = t + TPR * i;
+            if (rv && k < nkz) {
+              const T2 z = row[fft_pidx(k)];
+              O[k] = T2{z.x * sc, z.y * sc};
+            }
+          }
+        }
+      }
     }
     row_sync<TPRF>();  // this pair's LDS reads precede the next pair's writes
   }
@@ -2222,7 +2244,10 @@ static void zreal_launch(const ZRealArgs& a, const void* fields, const Twiddles&
   const long long nrows = static_cast<long long>(a.ny) * a.NX;
   const long long ngroups = (nrows + ZR - 1) / ZR;
   CH_CHECK(ngroups < (1LL << 31), "zreal: too many rows for one launch");
-  if (a.pres)
+  if (a.pres && a.spec_out)
+    hipLaunchKernelGGL((zreal_kernel<NN, T, true, true>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
+                       static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
+  else if (a.pres)
     hipLaunchKernelGGL((zreal_kernel<NN, T, true>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
                        static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
   else

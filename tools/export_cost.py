@@ -1,5 +1,5 @@
 """Cost of one plane_moments(), one gradient_sums(), one transport_moments(), one pressure solve (the
-device part of pressure_hat()), one pressure_moments() and one three-field all-plane physical_fields()
+device part of pressure_hat()), one pressure_moments(), one pressure_strain() and one three-field all-plane physical_fields()
 at 1024x385x1024 fp32, relative to one RK3 step in the same process.
 --skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out."""
 import json
@@ -62,6 +62,19 @@ for rep in range(5):
 res["pressure_moments_ms"] = ts
 res["pressure_moments_over_step"] = min(ts) / step_ms
 res["p_rms_centre"] = float(pm[0, 192] ** 0.5)
+# pressure strain: the solve, the export pass with the return trip of p' (one more single-field x-forward
+# per chunk) and the Parseval pass over p-hat' and the four (combine mode: five) fields it reads; host time
+# of the whole call (the device work, its launches, the 21 KB result copy and its synchronisation)
+ts = []
+for rep in range(5):
+    t0 = time.perf_counter()
+    ps = s.pressure_strain()
+    ts.append((time.perf_counter() - t0) * 1e3)
+res["pressure_strain_ms"] = ts
+res["pressure_strain_over_step"] = min(ts) / step_ms
+res["pressure_strain_over_pressure_moments"] = min(ts) / min(res["pressure_moments_ms"])
+res["pstrain_trace_over_max"] = float(abs(ps[0] + ps[1] + ps[2]).max() / abs(ps[:3]).max())
+res["pu_pstrain_vs_moments"] = float(abs(ps[4] - pm[1]).max() / abs(pm[1]).max())
 if "--skip-fields" in sys.argv:
     print(json.dumps(res))
     sys.exit(0)
