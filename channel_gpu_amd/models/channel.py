@@ -160,9 +160,23 @@ class ChannelFlow:
         of <p'p'>: ``ndarray (7, NY)``; one rank without a communicator."""
         return np.asarray(self.solver.pressure_strain())
 
+    def plane_spectra(self, pressure: bool = False) -> dict:
+        """One-dimensional spectra and co-spectra of the current state at every plane
+        (``statistics.SPECTRA_ROWS``: uu, vv, ww, uv, wxwx, wywy, wzwz, pp): ``ekx`` ``(8, NY, Kx + 1)``
+        by |kx| (+kx and -kx folded, summed over kz) and ``ekz`` ``(8, NY, nkz)`` by kz (summed over
+        kx), with the wavenumbers ``kx`` and ``kz``.  Summing either over its wavenumber gives the
+        plane mean of the product.  Any number of ranks; ``pressure``: also row ``pp`` (one rank
+        without a communicator; zero otherwise)."""
+        d = dict(self.solver.plane_spectra(bool(pressure)))
+        d["ekx"], d["ekz"] = np.asarray(d["ekx"]), np.asarray(d["ekz"])
+        d["kx"] = 2.0 * np.pi / self.cfg.LX * np.arange(d["ekx"].shape[-1])
+        d["kz"] = 2.0 * np.pi / self.cfg.LZ * np.arange(d["ekz"].shape[-1])
+        return d
+
     # ---- time-averaged statistics -------------------------------------------------------------
     def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False,
-                          pressure: bool = False, pressure_strain: bool = False):
+                          pressure: bool = False, pressure_strain: bool = False, spectra: bool = False,
+                          spectra_pressure: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
         ``moments``: also the third and fourth central moments (skewness / flatness profiles);
@@ -170,7 +184,9 @@ class ChannelFlow:
         the budgets of k and the Reynolds stresses; takes the plane moments too, for <v^3>);
         ``pressure``: also the pressure moments (p r.m.s., <p'u'>, <p'v>, pressure diffusion);
         ``pressure_strain``: also the pressure-strain terms (with ``budgets`` and ``pressure`` the
-        per-component budgets then close: ``closure_uu``, ``closure_vv``, ``closure_ww``, ``closure_uv``)."""
+        per-component budgets then close: ``closure_uu``, ``closure_vv``, ``closure_ww``, ``closure_uv``);
+        ``spectra``: also the 1-D spectra at every plane (``TurbulenceStatistics.spectra``; any number
+        of ranks), with row ``pp`` when ``spectra_pressure`` (one rank)."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -190,6 +206,9 @@ class ChannelFlow:
                     self.statistics.add_pressure(self.pressure_moments())
                 if pressure_strain:
                     self.statistics.add_pressure_strain(self.pressure_strain())
+                if spectra:
+                    sp = self.plane_spectra(spectra_pressure)
+                    self.statistics.add_spectra(sp["ekx"], sp["ekz"], sp["kx"], sp["kz"], self.cfg.NX, 2 * self.cfg.NZ - 2)
         return self.statistics
 
     def grid_points(self) -> int:

@@ -14,7 +14,9 @@ into vorticity r.m.s. profiles and the budgets of k and of the Reynolds stresses
 moments of the y-line Poisson solve (``Solver.pressure_moments``) into the pressure r.m.s., the
 pressure-velocity correlations and the pressure-diffusion terms of those budgets, and the Parseval
 sums of the spectral static pressure (``Solver.pressure_strain``) into the pressure-strain terms, with
-which the uu, vv, ww and uv budgets close component by component.
+which the uu, vv, ww and uv budgets close component by component.  The one-dimensional spectra at
+every plane (``Solver.plane_spectra``) are averaged into wall-unit spectra, premultiplied spectra and
+two-point correlations (``spectra``).
 """
 from __future__ import annotations
 
@@ -37,6 +39,9 @@ PRESSURE_TERMS = ("pdiff_k", "pdiff_vv", "pdiff_uv")
 # <p'u'>, <p'v> and the retained-band part of <p'p'>
 PSTRAIN_ROWS = ("ps_uu", "ps_vv", "ps_ww", "ps_uv", "pu", "pv", "pp_band")
 PSTRAIN_TERMS = ("pstrain_uu", "pstrain_vv", "pstrain_ww", "pstrain_uv")
+# rows of Solver.plane_spectra(): |u|^2, |v|^2, |w|^2, Re(u v*), |omega_x|^2, |omega_y|^2, |omega_z|^2,
+# |p'|^2 per |kx| and per kz at every plane
+SPECTRA_ROWS = ("uu", "vv", "ww", "uv", "wxwx", "wywy", "wzwz", "pp")
 
 
 class TurbulenceStatistics:
@@ -64,6 +69,68 @@ class TurbulenceStatistics:
         self.pres = np.zeros((len(PRESSURE_ROWS), n))
         self.nps = 0
         self.pstr = np.zeros((len(PSTRAIN_ROWS), n))
+        self.nsp = 0
+        self.ekx = self.ekz = self.kx = self.kz = None
+        self.nxz = (0, 0)
+
+    def add_spectra(self, ekx, ekz, kx, kz, nx: int | None = None, nz: int | None = None):
+        """One sample of the 1-D spectra at every plane (``Solver.plane_spectra``): ``ekx`` [8, NY, nkx]
+        by |kx| and ``ekz`` [8, NY, nkz] by kz (``SPECTRA_ROWS``) with their wavenumbers in solver
+        units.  ``nx``, ``nz``: the physical grid of the two-point correlations (default: twice the
+        highest wavenumber index, the smallest grid that holds the bins)."""
+        ekx, ekz = np.asarray(ekx, float), np.asarray(ekz, float)
+        n = self.y.size
+        if ekx.shape[:2] != (len(SPECTRA_ROWS), n) or ekz.shape[:2] != (len(SPECTRA_ROWS), n):
+            raise ValueError(f"spectra of shape {ekx.shape}, {ekz.shape}: expected ({len(SPECTRA_ROWS)}, {n}, nk)")
+        if self.nsp == 0:
+            self.ekx, self.ekz = np.zeros_like(ekx), np.zeros_like(ekz)
+            self.kx, self.kz = np.asarray(kx, float).copy(), np.asarray(kz, float).copy()
+            self.nxz = (int(nx) if nx else 2 * (ekx.shape[2] - 1), int(nz) if nz else 2 * (ekz.shape[2] - 1))
+        self.ekx += ekx
+        self.ekz += ekz
+        self.nsp += 1
+
+    def spectra(self) -> dict:
+        """Averaged 1-D spectra folded onto the lower half, in wall units.  The result is
+        two-dimensional (y, k), so it is kept out of ``profiles``:
+
+          y_plus                       [h]      from the nearest wall
+          kx_plus, kz_plus             [nk]     k nu / u_tau
+          lambda_x_plus, lambda_z_plus [nk]     2 pi / k+ (inf at k = 0)
+          E_kx[row], E_kz[row]         [h, nk]  energy per wavenumber bin (the sum over k is the plane
+                                                mean of the product): velocity rows in u_tau^2, vorticity
+                                                rows in u_tau^4 / nu^2, pp in u_tau^4; uv is folded
+                                                antisymmetrically like ``uvplus`` (but keeps its sign)
+          premult_kx[row], premult_kz[row]      k Phi(k) with the density Phi = E / dk: (k / dk) E
+          R_x[row], R_z[row]           [h, n/2 + 1]  two-point correlation coefficients of the
+                                                auto-spectra rows at 0 .. n/2 grid intervals
+          r_x_plus, r_z_plus           [n/2 + 1]  those separations"""
+        if self.nsp == 0 or self.n == 0:
+            raise ValueError("no spectra samples")
+        from ..reference.spectra import AUTO_ROWS, correlations
+
+        n = self.y.size
+        ut, nu = self.utau(), self.nu
+        h = (n + 1) // 2
+        lo = np.arange(h)
+        hi = n - 1 - lo
+        unit = {"uu": ut ** 2, "vv": ut ** 2, "ww": ut ** 2, "uv": ut ** 2, "wxwx": ut ** 4 / nu ** 2,
+                "wywy": ut ** 4 / nu ** 2, "wzwz": ut ** 4 / nu ** 2, "pp": ut ** 4}
+        out = {"y_plus": (1.0 + self.y[lo]) * ut / nu, "E_kx": {}, "E_kz": {}, "premult_kx": {}, "premult_kz": {},
+               "R_x": {}, "R_z": {}}
+        for d, k, e, nn in (("x", self.kx, self.ekx / self.nsp, self.nxz[0]), ("z", self.kz, self.ekz / self.nsp, self.nxz[1])):
+            out[f"k{d}_plus"] = k * nu / ut
+            with np.errstate(divide="ignore"):
+                out[f"lambda_{d}_plus"] = 2.0 * np.pi / out[f"k{d}_plus"]
+            idx = k / k[1] if k.size > 1 else np.zeros_like(k)
+            out[f"r_{d}_plus"] = np.arange(nn // 2 + 1) * (2.0 * np.pi / k[1] / nn if k.size > 1 else 0.0) * ut / nu
+            for q, row in enumerate(SPECTRA_ROWS):
+                a = 0.5 * (e[q][lo] + (-1.0 if row == "uv" else 1.0) * e[q][hi]) / unit[row]
+                out[f"E_k{d}"][row] = a
+                out[f"premult_k{d}"][row] = idx * a
+                if row in AUTO_ROWS:
+                    out[f"R_{d}"][row] = correlations(a, nn)
+        return out
 
     def add_pressure_strain(self, ps):
         """One sample of the pressure-strain sums [7, NY] (``PSTRAIN_ROWS``)."""

@@ -74,7 +74,7 @@ PYBIND11_MODULE(_core, m) {
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
       RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every)
-      RW(pstrain_every);
+      RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -358,7 +358,32 @@ PYBIND11_MODULE(_core, m) {
              std::copy(t.begin(), t.end(), a.mutable_data());
              return a;
            },
-           "Parseval plane sums ps_uu, ps_vv, ps_ww, ps_uv, pu, pv, pp_band of p' with the strain factors: (7, NY) (one rank)");
+           "Parseval plane sums ps_uu, ps_vv, ps_ww, ps_uv, pu, pv, pp_band of p' with the strain factors: (7, NY) (one rank)")
+      .def("plane_spectra",
+           [](Solver& s, bool pressure) {
+             // the arrays view the result in place (a capsule owns it): no second host copy
+             auto sp = std::make_unique<Solver::PlaneSpectra>();
+             {
+               py::gil_scoped_release r;
+               *sp = s.plane_spectra(pressure);
+             }
+             Solver::PlaneSpectra* raw = sp.release();
+             py::capsule owner(raw, [](void* q) { delete static_cast<Solver::PlaneSpectra*>(q); });
+             const Plan& p = s.plan();
+             auto arr = [&](std::vector<double>& v, int nk) {
+               return py::array_t<double>({static_cast<py::ssize_t>(kYSpecRows), static_cast<py::ssize_t>(p.NY),
+                                           static_cast<py::ssize_t>(nk)}, v.data(), owner);
+             };
+             py::dict d;
+             d["rows"] = raw->rows;
+             d["ekx"] = arr(raw->ekx, p.Kx + 1);
+             d["ekz"] = arr(raw->ekz, p.nkz);
+             return d;
+           },
+           py::arg("pressure") = false,
+           "1-D spectra and co-spectra uu, vv, ww, uv, wxwx, wywy, wzwz, pp of the current state at every plane: ekx "
+           "(8, NY, Kx+1) by |kx|, ekz (8, NY, nkz) by kz, global over the communicator; row pp is zero unless "
+           "pressure (one rank)");
 
   py::class_<ProcInfo>(m, "ProcInfo")
       .def(py::init<>())

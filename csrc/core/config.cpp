@@ -229,6 +229,8 @@ Config Config::from_tree(const ConfigTree& t) {
   c.budget_every = static_cast<int>(t.get_int(pick(t, "budget_every"), c.budget_every));
   c.pressure_every = static_cast<int>(t.get_int(pick(t, "pressure_every"), c.pressure_every));
   c.pstrain_every = static_cast<int>(t.get_int(pick(t, "pstrain_every"), c.pstrain_every));
+  c.yspectra_every = static_cast<int>(t.get_int(pick(t, "yspectra_every"), c.yspectra_every));
+  c.yspectra_pressure = static_cast<int>(t.get_int(pick(t, "yspectra_pressure"), c.yspectra_pressure));
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -326,8 +328,9 @@ void Config::validate() const {
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
                spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
-               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0,
+               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0 && yspectra_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
+  CH_CHECK(yspectra_pressure == 0 || yspectra_pressure == 1, "yspectra_pressure must be 0|1");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
   CH_CHECK(rollback_cfl_factor > 0 && rollback_cfl_factor <= 1, "rollback_cfl_factor must be in (0, 1]");
   CH_CHECK(max_rollbacks >= 0, "max_rollbacks must be >= 0");
@@ -369,6 +372,7 @@ std::string Config::to_string() const {
   o << "  budget_every = " << budget_every << ";\n";
   o << "  pressure_every = " << pressure_every << ";\n";
   o << "  pstrain_every = " << pstrain_every << ";\n";
+  o << "  yspectra_every = " << yspectra_every << ";\n  yspectra_pressure = " << yspectra_pressure << ";\n";
   o << "};\n";
   return o.str();
 }

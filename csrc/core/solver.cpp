@@ -452,9 +452,13 @@ void Solver::free_all() {
   h_tdt_ = nullptr;
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
                   static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
-                  static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_)})
+                  static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_),
+                  static_cast<void*>(d_yspec_)})
     if (p) (void)hipFree(p);
   d_pstr_ = nullptr;
+  d_yspec_ = nullptr;
+  if (h_yspec_) (void)hipHostFree(h_yspec_);
+  h_yspec_ = nullptr;
   state_ = out_ = phys_ = xbuf_ = zbuf_ = dscal_ = snap_ = d_spec_ = d_sym_ = d_real_ = nullptr;
   d_mom_ = nullptr;
   d_grad_ = nullptr;
@@ -2169,6 +2173,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (cfg_.budget_every > 0 && nstep_ % cfg_.budget_every == 0) write_budget_files();
     if (cfg_.pressure_every > 0 && nstep_ % cfg_.pressure_every == 0) write_pressure_files();
     if (cfg_.pstrain_every > 0 && nstep_ % cfg_.pstrain_every == 0) write_pstrain_files();
+    if (cfg_.yspectra_every > 0 && nstep_ % cfg_.yspectra_every == 0) write_yspectra_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();
       prepare();
@@ -2888,6 +2893,113 @@ std::vector<double> Solver::gradient_sums() {
   return g;
 }
 
+// ---- spectra at every plane -------------------------------------------------------------------------
+// As gradient_sums(): the same fields read in place, one launch per kx sub-block on the compute
+// stream, one all-reduce over both arrays; nothing the next step reads is written.  With the pressure
+// row the device part of static_pressure_hat() runs first (it writes d_pres_ and the step's scratch).
+Solver::PlaneSpectra Solver::plane_spectra(bool pressure) {
+  CH_CHECK(!pressure || !comm_, "plane_spectra: the pressure row is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const size_t nx = static_cast<size_t>(kYSpecRows) * p.NY * (p.Kx + 1), nz = static_cast<size_t>(kYSpecRows) * p.NY * p.nkz;
+  if (!d_yspec_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_yspec_), (nx + nz) * sizeof(double)));
+  if (!h_yspec_) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_yspec_), (nx + nz) * sizeof(double), hipHostMallocDefault));
+  if (!prepared_) prepare();
+  if (pressure) static_pressure_device();
+  HIP_CHECK(hipMemsetAsync(d_yspec_, 0, (nx + nz) * sizeof(double), s_comp_));
+  YSpectraArgs a;
+  const int nf = bwd_fields();
+  for (int f = 0; f < nf; ++f) a.f[f] = in_field(f);
+  if (pressure) a.p = static_cast<const char*>(d_pres_) + spec_ * esz_;
+  a.combine = combine_ ? 1 : 0;
+  a.ax = p.ax;
+  a.az = p.az;
+  a.N = p.NY;
+  a.nkz_loc = p.nkz_loc;
+  a.kz0 = p.kz0;
+  a.nkzs = nkzs_;
+  a.kzb = kzb_;
+  a.nkx = p.nkx;
+  a.Kx = p.Kx;
+  a.nkz = p.nkz;
+  a.ekx = d_yspec_;
+  a.ekz = d_yspec_ + nx;
+  for (int b = 0; b < nkb_; ++b) {
+    YSpectraArgs ab = a;
+    for (int f = 0; f < nf; ++f) ab.f[f] = static_cast<const char*>(a.f[f]) + kb_off_[b] * esz_;
+    if (a.p) ab.p = static_cast<const char*>(a.p) + kb_off_[b] * esz_;
+    ab.nkx_loc = kb_cnt_[b];
+    ab.kx0 = p.kx0 + kb_start_[b];
+    yspectra_accumulate(ab, fp64_, s_comp_);
+  }
+  if (comm_) {
+    HIP_CHECK(hipEventRecord(ev_stats_, s_comp_));
+    HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_stats_, 0));
+    comm_->allreduce_sum_f64(d_yspec_, nx + nz, s_comm_);
+    wait(s_comm_);
+  }
+  PlaneSpectra out;
+  out.rows = {"uu", "vv", "ww", "uv", "wxwx", "wywy", "wzwz", "pp"};
+  // (through pinned memory: a copy into fresh pageable vectors runs at a fraction of the link's rate)
+  HIP_CHECK(hipMemcpyAsync(h_yspec_, d_yspec_, (nx + nz) * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
+  wait(s_comp_);
+  out.ekx.assign(h_yspec_, h_yspec_ + nx);
+  out.ekz.assign(h_yspec_ + nx, h_yspec_ + nx + nz);
+  return out;
+}
+
+namespace {
+// Header of a NumPy v1.0 file: magic, version, little-endian length, the dict padded with spaces to a
+// multiple of 64 bytes in all and newline-terminated.  shape: "(a, b, c)".
+std::string npy_header(const char* descr, const std::string& shape) {
+  std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape + ", }";
+  const size_t hlen = (10 + dict.size() + 1 + 63) / 64 * 64 - 10;
+  dict.resize(hlen - 1, ' ');
+  dict.push_back('\n');
+  std::string h("\x93NUMPY\x01\x00", 8);
+  h.push_back(static_cast<char>(hlen & 0xff));
+  h.push_back(static_cast<char>(hlen >> 8));
+  return h + dict;
+}
+}  // namespace
+
+// <path>YSPEC_KX_<step>.npy (8, NY, Kx+1) and <path>YSPEC_KZ_<step>.npy (8, NY, nkz), float64, and a
+// sidecar <path>YSPEC_<step>.json; every rank takes part in the sums, rank 0 writes
+void Solver::write_yspectra_files() {
+  bool pres = cfg_.yspectra_pressure != 0;
+  if (pres && comm_) {
+    if (!yspec_note_ && plan_.rank == 0)
+      std::fprintf(stderr, "[channel] yspectra_pressure: row pp of YSPEC_*.npy skipped (the pressure solve is single-rank)\n");
+    yspec_note_ = true;
+    pres = false;
+  }
+  const PlaneSpectra sp = plane_spectra(pres);
+  if (plan_.rank != 0) return;
+  const Plan& p = plan_;
+  char step[16];
+  std::snprintf(step, sizeof(step), "%08ld", nstep_);
+  auto put = [&](const char* name, const std::vector<double>& v, int nk) {
+    const std::string fn = cfg_.path + name + step + ".npy";
+    std::ofstream f(fn, std::ios::binary | std::ios::trunc);
+    CH_CHECK(f.good(), "cannot open '" << fn << "'");
+    const std::string h = npy_header("<f8", "(" + std::to_string(kYSpecRows) + ", " + std::to_string(p.NY) + ", " + std::to_string(nk) + ")");
+    f.write(h.data(), static_cast<std::streamsize>(h.size()));
+    f.write(reinterpret_cast<const char*>(v.data()), static_cast<std::streamsize>(v.size() * sizeof(double)));
+    f.close();
+    CH_CHECK(!f.fail(), "writing '" << fn << "' failed");
+  };
+  put("YSPEC_KX_", sp.ekx, p.Kx + 1);
+  put("YSPEC_KZ_", sp.ekz, p.nkz);
+  double hv[2];
+  HIP_CHECK(hipMemcpy(hv, d_dt_, sizeof(hv), hipMemcpyDeviceToHost));
+  std::ofstream js(cfg_.path + "YSPEC_" + step + ".json");
+  js.precision(17);
+  js << "{\"step\": " << nstep_ << ", \"time\": " << hv[1] << ", \"rows\": [";
+  for (size_t k = 0; k < sp.rows.size(); ++k) js << (k ? ", " : "") << "\"" << sp.rows[k] << "\"";
+  js << "], \"pressure\": " << (pres ? "true" : "false") << ", \"ax\": " << p.ax << ", \"az\": " << p.az << ", \"y\": [";
+  for (int j = 0; j < p.NY; ++j) js << (j ? ", " : "") << grid_.y[j];
+  js << "], \"Re\": " << cfg_.Re << "}\n";
+}
+
 // one line of NY values per call and file, as write_stats_files: the vorticity r.m.s., the
 // dissipation 2 nu g of the uu, vv, ww, uv budgets and (one rank without a communicator) the triple
 // products of the turbulent transport
@@ -2934,25 +3046,16 @@ void Solver::write_field_files() {
   std::snprintf(step, sizeof(step), "%08ld", nstep_);
   const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
   const size_t plane = static_cast<size_t>(p.NX) * p.Nzp;
-  // header: magic, version 1.0, little-endian length, dict padded with spaces to a multiple of 64
-  // bytes in all, newline-terminated
-  std::string dict = std::string("{'descr': '") + (fp64_ ? "<f8" : "<f4") + "', 'fortran_order': False, 'shape': (" +
-                     std::to_string(planes.size()) + ", " + std::to_string(p.NX) + ", " + std::to_string(p.Nzp) + "), }";
-  const size_t hlen = (10 + dict.size() + 1 + 63) / 64 * 64 - 10;
-  dict.resize(hlen - 1, ' ');
-  dict.push_back('\n');
+  const std::string head = npy_header(fp64_ ? "<f8" : "<f4", "(" + std::to_string(planes.size()) + ", " + std::to_string(p.NX) +
+                                                                 ", " + std::to_string(p.Nzp) + ")");
   std::vector<std::ofstream> files;
   for (const std::string& nm : names) {
     files.emplace_back(cfg_.path + "FIELD_" + nm + "_" + step + ".npy", std::ios::binary | std::ios::trunc);
     std::ofstream& f = files.back();
     CH_CHECK(f.good(), "cannot open field file for '" << nm << "' under '" << cfg_.path << "'");
-    const char magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-    f.write(magic, 8);
-    const unsigned char len[2] = {static_cast<unsigned char>(hlen & 0xff), static_cast<unsigned char>(hlen >> 8)};
-    f.write(reinterpret_cast<const char*>(len), 2);
-    f.write(dict.data(), static_cast<std::streamsize>(dict.size()));
+    f.write(head.data(), static_cast<std::streamsize>(head.size()));
   }
-  const std::streamoff data0 = static_cast<std::streamoff>(10 + hlen);
+  const std::streamoff data0 = static_cast<std::streamoff>(head.size());
   std::vector<std::vector<size_t>> pos(p.NY);
   for (size_t i = 0; i < planes.size(); ++i) pos[planes[i]].push_back(i);
   std::vector<char> pbuf;

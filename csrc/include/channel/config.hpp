@@ -93,6 +93,8 @@ struct Config {
   int moments_every = 0;               // 0 = off; skewness / flatness profiles of u, v, w (*SKEW.dat, *FLAT.dat)
   int pressure_every = 0;              // 0 = off; pressure r.m.s. and pressure-velocity profiles (PRMS.dat, PU.dat, PV.dat; one rank)
   int pstrain_every = 0;               // 0 = off; pressure-strain profiles of the uu, vv, ww, uv budgets (PS_*.dat; one rank)
+  int yspectra_every = 0;              // 0 = off; 1-D spectra and co-spectra at every plane (YSPEC_KX_<step>.npy, YSPEC_KZ_<step>.npy, YSPEC_<step>.json; any P)
+  int yspectra_pressure = 0;           // 1 = also the pressure row of those spectra (one rank)
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});

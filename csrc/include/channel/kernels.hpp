@@ -400,6 +400,27 @@ struct PStrainArgs {
   double* sums = nullptr;             // [kPStrainRows][N]
 };
 void pstrain_accumulate(const PStrainArgs& a, bool fp64, hipStream_t s);
+// One-dimensional spectra and co-spectra at every plane: one local block of spectral fields is read
+// once, like the gradient sums (same inputs, weights and masks: kz = 0 once, kz > 0 twice, the mean
+// line and the padded lines skipped; products and sums in double), and per plane the products are
+// accumulated (+=) by |kx| (+kx and -kx folded, summed over kz) and by global kz (summed over kx).
+// Summing either output over its wavenumber gives the plane mean of the product.  Rows: |u|^2, |v|^2,
+// |w|^2, Re(u v*), |omega_x|^2, |omega_y|^2, |omega_z|^2, |p|^2 (left untouched when p is null).
+constexpr int kYSpecRows = 8;
+struct YSpectraArgs {
+  // as GradSumArgs: u, v, w, omega_x, omega_y, omega_z, or the five combine inputs
+  const void* f[6] = {};
+  const void* p = nullptr;            // p-hat' in the layout of the fields, or null
+  int combine = 0;
+  double ax = 1.0, az = 2.0;
+  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
+  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
+  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
+  int nkx = 0, Kx = 0, nkz = 0;       // global retained counts
+  double* ekx = nullptr;              // [kYSpecRows][N][Kx + 1]
+  double* ekz = nullptr;              // [kYSpecRows][N][nkz]
+};
+void yspectra_accumulate(const YSpectraArgs& a, bool fp64, hipStream_t s);
 // element (local kx 0, kz 0) of every plane y < N of one spectral field (lines = nkx_loc * nkzs) := 0
 void zero_mean_line(void* q, int N, int kzb, int lines, bool fp64, hipStream_t s);
 // fault injection (tests): element `elem` of a complex field becomes NaN

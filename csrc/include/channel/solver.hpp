@@ -157,6 +157,16 @@ class Solver {
   // the pressure-strain terms of the uu, vv, ww, uv budgets, <p'u'>, <p'v> and the retained-band part
   // of <p'p'>); one rank without a communicator
   std::vector<double> pressure_strain();
+  // One-dimensional spectra and co-spectra of the current state at every plane (kernels.hpp
+  // YSpectraArgs): ekx [kYSpecRows][NY][Kx+1] by |kx| (summed over kz), ekz [kYSpecRows][NY][nkz] by
+  // kz (summed over kx); rows uu, vv, ww, uv, wxwx, wywy, wzwz, pp.  Global (any communicator;
+  // all-reduced like gradient_sums()).  pressure: also row pp, from static_pressure_hat()'s device part
+  // (one rank without a communicator); otherwise that row is zero.
+  struct PlaneSpectra {
+    std::vector<std::string> rows;
+    std::vector<double> ekx, ekz;
+  };
+  PlaneSpectra plane_spectra(bool pressure = false);
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -231,6 +241,7 @@ class Solver {
   // Pi of the current state into field 0 of d_pres_ (device part of pressure_hat)
   void pressure_device(double* ms = nullptr);
   void write_pstrain_files();
+  void write_yspectra_files();
   // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat)
   void static_pressure_device();
   // one device spectral field as canonical [y][kx][kz]; refuses non-zero padding of the device layout
@@ -398,6 +409,9 @@ class Solver {
   bool pres_note_ = false;    // the "pressure files skipped" note has been printed
   double* d_pstr_ = nullptr;  // pressure strain: [kPStrainRows][NY]
   bool pstr_note_ = false;    // the "pressure-strain files skipped" note has been printed
+  double* d_yspec_ = nullptr;  // plane spectra: ekx [kYSpecRows][NY][Kx+1], then ekz [kYSpecRows][NY][nkz]
+  double* h_yspec_ = nullptr;  // pinned host copy of d_yspec_ (the result is 17 MB at the headline grid)
+  bool yspec_note_ = false;   // the "pressure row skipped" note has been printed
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 
   bool use_graph_ = true;

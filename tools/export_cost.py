@@ -1,6 +1,6 @@
 """Cost of one plane_moments(), one gradient_sums(), one transport_moments(), one pressure solve (the
-device part of pressure_hat()), one pressure_moments(), one pressure_strain() and one three-field all-plane physical_fields()
-at 1024x385x1024 fp32, relative to one RK3 step in the same process.
+device part of pressure_hat()), one pressure_moments(), one pressure_strain(), one plane_spectra() without and with
+the pressure row and one three-field all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
 --skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out."""
 import json
 import os
@@ -75,6 +75,22 @@ res["pressure_strain_over_step"] = min(ts) / step_ms
 res["pressure_strain_over_pressure_moments"] = min(ts) / min(res["pressure_moments_ms"])
 res["pstrain_trace_over_max"] = float(abs(ps[0] + ps[1] + ps[2]).max() / abs(ps[:3]).max())
 res["pu_pstrain_vs_moments"] = float(abs(ps[4] - pm[1]).max() / abs(pm[1]).max())
+# plane spectra: the read of gradient_sums() with a sum per (plane, |kx|) and (plane, kz); host time of the
+# whole call (the 16.8 MB memset, the launch, the 16.8 MB result copy and its synchronisation), without and
+# with the pressure row (then the device part of static_pressure_hat() first and a seventh field read)
+res["plane_spectra_result_bytes"] = 8 * cfg.NY * (cfg.NX // 3 + 1 + nkz) * 8
+for name, flag in (("plane_spectra", False), ("plane_spectra_pressure", True)):
+    ts = []
+    for rep in range(5):
+        t0 = time.perf_counter()
+        sp = s.plane_spectra(flag)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res[name + "_ms"] = ts
+    res[name + "_over_step"] = min(ts) / step_ms
+    res[name + "_over_gradient_sums"] = min(ts) / min(res["gradient_sums_ms"])
+g = s.gradient_sums()
+res["plane_spectra_wxwx_sum_vs_gradient_sums"] = float(abs(sp["ekx"][4].sum(axis=-1) - g[0]).max() / abs(g[0]).max())
+res["plane_spectra_pp_sum_vs_pstrain"] = float(abs(sp["ekz"][7].sum(axis=-1) - ps[6]).max() / abs(ps[6]).max())
 if "--skip-fields" in sys.argv:
     print(json.dumps(res))
     sys.exit(0)
