@@ -35,6 +35,32 @@ py::array_t<double> vec(const std::vector<double>& v) {
   return a;
 }
 
+// a per-plane diagnostic of the solver (the call without the GIL) as a (rows, NY) array
+py::array_t<double> profile_rows(Solver& s, std::vector<double> (Solver::*call)(), int rows) {
+  std::vector<double> v;
+  {
+    py::gil_scoped_release r;
+    v = (s.*call)();
+  }
+  py::array_t<double> a({static_cast<py::ssize_t>(rows), static_cast<py::ssize_t>(s.plan().NY)});
+  std::copy(v.begin(), v.end(), a.mutable_data());
+  return a;
+}
+
+// a canonical spectral field of the solver (the call without the GIL) as a (NY, nkx_loc, nkz_loc) array
+py::array_t<std::complex<double>> canonical_field(Solver& s, std::vector<std::complex<double>> (Solver::*call)()) {
+  std::vector<std::complex<double>> v;
+  {
+    py::gil_scoped_release r;
+    v = (s.*call)();
+  }
+  const Plan& p = s.plan();
+  py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(p.NY), static_cast<py::ssize_t>(p.nkx_loc),
+                                       static_cast<py::ssize_t>(p.nkz_loc)});
+  std::copy(v.begin(), v.end(), a.mutable_data());
+  return a;
+}
+
 py::bytes new_uid() { return py::bytes(Comm::new_unique_id()); }
 
 int device_count() {
@@ -269,95 +295,28 @@ PYBIND11_MODULE(_core, m) {
            py::arg("planes"), py::arg("names"),
            "physical-space planes of the current state: name -> (nplanes, NX, Nzp) float64 (one rank)")
       .def("plane_moments",
-           [](Solver& s) {
-             std::vector<double> m;
-             {
-               py::gil_scoped_release r;
-               m = s.plane_moments();
-             }
-             py::array_t<double> a({static_cast<py::ssize_t>(kMomRows), static_cast<py::ssize_t>(s.plan().NY)});
-             std::copy(m.begin(), m.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return profile_rows(s, &Solver::plane_moments, kMomRows); },
            "plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4: (11, NY) (one rank)")
       .def("gradient_sums",
-           [](Solver& s) {
-             std::vector<double> g;
-             {
-               py::gil_scoped_release r;
-               g = s.gradient_sums();
-             }
-             py::array_t<double> a({static_cast<py::ssize_t>(kGradRows), static_cast<py::ssize_t>(s.plan().NY)});
-             std::copy(g.begin(), g.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return profile_rows(s, &Solver::gradient_sums, kGradRows); },
            "velocity-gradient plane sums wxwx, wywy, wzwz, guu, gvv, gww, guv of the current state: (7, NY), "
            "raw sums (no nu, no factor 2), global over the communicator")
       .def("transport_moments",
-           [](Solver& s) {
-             std::vector<double> t;
-             {
-               py::gil_scoped_release r;
-               t = s.transport_moments();
-             }
-             py::array_t<double> a({static_cast<py::ssize_t>(kTripleRows), static_cast<py::ssize_t>(s.plan().NY)});
-             std::copy(t.begin(), t.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return profile_rows(s, &Solver::transport_moments, kTripleRows); },
            "plane means of u'u'v, wwv, u'vv: (3, NY) (one rank)")
       .def("pressure_hat",
-           [](Solver& s) {
-             std::vector<std::complex<double>> v;
-             {
-               py::gil_scoped_release r;
-               v = s.pressure_hat();
-             }
-             const Plan& p = s.plan();
-             py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(p.NY), static_cast<py::ssize_t>(p.nkx_loc),
-                                                  static_cast<py::ssize_t>(p.nkz_loc)});
-             std::copy(v.begin(), v.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return canonical_field(s, &Solver::pressure_hat); },
            "Pi = p + |u|^2 / 2 of the current state per (kx, kz) line, (NY, nkx, nkz), zero on the mean line (one rank)")
       .def("pressure_timing", &Solver::pressure_timing, py::call_guard<py::gil_scoped_release>(),
            "device ms of one pressure solve: [transform stage, y-line Poisson kernel] (one rank)")
       .def("pressure_moments",
-           [](Solver& s) {
-             std::vector<double> t;
-             {
-               py::gil_scoped_release r;
-               t = s.pressure_moments();
-             }
-             py::array_t<double> a({static_cast<py::ssize_t>(4), static_cast<py::ssize_t>(s.plan().NY)});
-             std::copy(t.begin(), t.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return profile_rows(s, &Solver::pressure_moments, 4); },
            "plane means p'p', p'u', p'v, p'w of the fluctuating static pressure: (4, NY) (one rank)")
       .def("static_pressure_hat",
-           [](Solver& s) {
-             std::vector<std::complex<double>> v;
-             {
-               py::gil_scoped_release r;
-               v = s.static_pressure_hat();
-             }
-             const Plan& p = s.plan();
-             py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(p.NY), static_cast<py::ssize_t>(p.nkx_loc),
-                                                  static_cast<py::ssize_t>(p.nkz_loc)});
-             std::copy(v.begin(), v.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return canonical_field(s, &Solver::static_pressure_hat); },
            "the fluctuating static pressure p' per (kx, kz) line, (NY, nkx, nkz), zero on the mean line (one rank)")
       .def("pressure_strain",
-           [](Solver& s) {
-             std::vector<double> t;
-             {
-               py::gil_scoped_release r;
-               t = s.pressure_strain();
-             }
-             py::array_t<double> a({static_cast<py::ssize_t>(kPStrainRows), static_cast<py::ssize_t>(s.plan().NY)});
-             std::copy(t.begin(), t.end(), a.mutable_data());
-             return a;
-           },
+           [](Solver& s) { return profile_rows(s, &Solver::pressure_strain, kPStrainRows); },
            "Parseval plane sums ps_uu, ps_vv, ps_ww, ps_uv, pu, pv, pp_band of p' with the strain factors: (7, NY) (one rank)")
       .def("plane_spectra",
            [](Solver& s, bool pressure) {

@@ -2268,867 +2268,6 @@ void Solver::inject_nan(int f) {
   HIP_CHECK(hipStreamSynchronize(s_comp_));
 }
 
-// ---- spectra --------------------------------------------------------------------------------------
-Solver::Spectra Solver::spectra() {
-  const Plan& p = plan_;
-  Spectra out;
-  out.planes = cfg_.spectra_plane_list();
-  const int np = static_cast<int>(out.planes.size());
-  const size_t nx = 3 * np * (p.Kx + 1), nz = 3 * np * p.nkz, nm = 3 * static_cast<size_t>(p.nkx) * p.nkz;
-  const size_t need = (nx + nz + nm) * sizeof(double) + np * sizeof(int);
-  if (spec_n_ < need) {
-    if (d_spec_) HIP_CHECK(hipFree(d_spec_));
-    HIP_CHECK(hipMalloc(&d_spec_, need));
-    spec_n_ = need;
-  }
-  double* ekx = static_cast<double*>(d_spec_);
-  double* ekz = ekx + nx;
-  double* map = ekz + nz;
-  int* planes = reinterpret_cast<int*>(map + nm);
-  HIP_CHECK(hipMemsetAsync(d_spec_, 0, (nx + nz + nm) * sizeof(double), s_comp_));
-  HIP_CHECK(hipMemcpyAsync(planes, out.planes.data(), np * sizeof(int), hipMemcpyHostToDevice, s_comp_));
-  SpectraArgs a;
-  a.dv = field_ptr(OUT0);
-  a.v = field_ptr(OUT1);
-  a.om = field_ptr(OMEGA);
-  a.ax = p.ax;
-  a.az = p.az;
-  a.combine = combine_ ? 1 : 0;
-  a.u = field_ptr(OUT0);
-  a.w = field_ptr(OUT2);
-  a.lines = p.nkx_loc * nkzs_;
-  a.nkx_loc = p.nkx_loc;
-  a.kx0 = p.kx0;
-  a.nkz_loc = p.nkz_loc;
-  a.nkzs = nkzs_;
-  a.kzb = kzb_;
-  a.kz0 = p.kz0;
-  a.nkx = p.nkx;
-  a.Kx = p.Kx;
-  a.nkz = p.nkz;
-  a.planes = planes;
-  a.nplanes = np;
-  a.ekx = ekx;
-  a.ekz = ekz;
-  a.map = map;
-  for (int b = 0; b < nkb_; ++b) {  // per kx sub-block (accumulating; map rows are disjoint)
-    SpectraArgs ab = a;
-    const size_t off = kb_off_[b] * esz_;
-    ab.dv = static_cast<const char*>(a.dv) + off;
-    ab.v = static_cast<const char*>(a.v) + off;
-    ab.om = static_cast<const char*>(a.om) + off;
-    ab.u = static_cast<const char*>(a.u) + off;
-    ab.w = static_cast<const char*>(a.w) + off;
-    ab.lines = kb_cnt_[b] * nkzs_;
-    ab.nkx_loc = kb_cnt_[b];
-    ab.kx0 = p.kx0 + kb_start_[b];
-    spectra_accumulate(ab, fp64_, s_comp_);
-  }
-  if (comm_) {
-    HIP_CHECK(hipEventRecord(ev_stats_, s_comp_));
-    HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_stats_, 0));
-    comm_->allreduce_sum_f64(ekx, nx + nz + nm, s_comm_);
-    wait(s_comm_);
-  }
-  synchronize();
-  out.ekx.resize(nx);
-  out.ekz.resize(nz);
-  out.map.resize(nm);
-  HIP_CHECK(hipMemcpy(out.ekx.data(), ekx, nx * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(out.ekz.data(), ekz, nz * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(out.map.data(), map, nm * sizeof(double), hipMemcpyDeviceToHost));
-  return out;
-}
-
-void Solver::write_spectra_files(const Spectra& sp) {
-  if (plan_.rank != 0) return;
-  const Plan& p = plan_;
-  const int np = static_cast<int>(sp.planes.size());
-  const double N2 = static_cast<double>(p.NX) * p.Nzp;
-  // reference layout (statistics.cu:272-320): NX rows (FFT-order kx) x NZ columns of |q|^2 in the
-  // file units (N2 * coefficient), plane planes[0]; overwritten each time like the reference's "w"
-  const char* maps[3] = {"Uspec.dat", "Vspec.dat", "Wspec.dat"};
-  for (int q = 0; q < 3; ++q) {
-    std::ofstream f(cfg_.path + maps[q]);
-    std::vector<int> ig_of_pos(p.NX, -1);
-    for (int i = 0; i < p.nkx; ++i) ig_of_pos[p.kx_fft_pos(i)] = i;
-    for (int x = 0; x < p.NX; ++x) {
-      for (int kz = 0; kz < p.NZ; ++kz) {
-        double v = 0.0;
-        if (ig_of_pos[x] >= 0 && kz < p.nkz) v = sp.map[(static_cast<size_t>(q) * p.nkx + ig_of_pos[x]) * p.nkz + kz];
-        f << " " << std::fixed << v * N2 * N2;
-      }
-      f << " \n";
-    }
-  }
-  // time series of 1-D spectra (true-coefficient units): one line per (plane, component)
-  auto app = [&](const char* name) { return std::ofstream(cfg_.path + name, std::ios::app); };
-  auto fx = app("SPECTRA_KX.dat");
-  auto fz = app("SPECTRA_KZ.dat");
-  double hv[2];
-  HIP_CHECK(hipMemcpy(hv, d_dt_, sizeof(hv), hipMemcpyDeviceToHost));
-  for (int pl = 0; pl < np; ++pl)
-    for (int q = 0; q < 3; ++q) {
-      fx << nstep_ << " " << std::scientific << hv[1] << " " << sp.planes[pl] << " " << "uvw"[q];
-      for (int k = 0; k <= p.Kx; ++k) fx << " " << sp.ekx[(static_cast<size_t>(q) * np + pl) * (p.Kx + 1) + k];
-      fx << "\n";
-      fz << nstep_ << " " << std::scientific << hv[1] << " " << sp.planes[pl] << " " << "uvw"[q];
-      for (int k = 0; k < p.nkz; ++k) fz << " " << sp.ekz[(static_cast<size_t>(q) * np + pl) * p.nkz + k];
-      fz << "\n";
-    }
-}
-
-// ---- physical-space export ------------------------------------------------------------------------
-// Between steps out_ (and the state) hold K-SPEC's outputs of the current state (as spectra()
-// relies on) and phys_ is scratch; everything goes on the compute stream behind whatever is queued
-// and touches nothing the next step reads, so the step graphs stay valid.
-// The x-backward addresses any plane range of the fields: rows spec_y0 + y through spec_row_off in
-// the blocked layout, planes past ny clamped at the loads and masked at the stores (also in the
-// plane tiles of the wide kernels), so a run of planes is transformed as it is requested.
-void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
-                           const std::function<void(int, int, const void*)>& sink, double* d_triple, bool pres,
-                           double* d_pmom) {
-  CH_CHECK(!comm_, "physical-space export is single-rank: it needs a solver without a communicator");
-  const Plan& p = plan_;
-  if (!prepared_) prepare();
-  // pressure mode: u, v, w and Pi (field 0 of d_pres_, x-transformed into slot 3 of the scratch); the
-  // solve runs first, its transform stage uses the same scratch
-  CH_CHECK(!pres || (nf == 4 && (out_mask & 7u) == (out_mask & ~8u) && !d_triple), "export: the pressure mode takes u, v, w, p");
-  if (pres) pressure_device();
-  const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
-  const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
-  const size_t plane = static_cast<size_t>(p.NX) * p.Nzp;
-  int nslots = 0;
-  for (int f = 0; f < 6; ++f) nslots += (out_mask >> f) & 1u;
-  if (nslots) {
-    const size_t need = static_cast<size_t>(nslots) * cap * plane * tsz;
-    if (real_n_ < need) {
-      HIP_CHECK(hipStreamSynchronize(s_comp_));
-      if (d_real_) HIP_CHECK(hipFree(d_real_));
-      d_real_ = nullptr;
-      real_n_ = 0;
-      HIP_CHECK(hipMalloc(&d_real_, need));
-      real_n_ = need;
-    }
-  }
-  XArgs xa = x_args();
-  const XSrc src = x_src_local(xa);
-  std::vector<char> host;
-  for (size_t i = 0; i < ys.size();) {
-    size_t j = i + 1;
-    while (j < ys.size() && ys[j] == ys[j - 1] + 1 && static_cast<int>(j - i) < cap) ++j;
-    const int y0 = ys[i], ny = static_cast<int>(j - i);
-    i = j;
-    XArgs xc;
-    XSrc sc;
-    x_chunk(xa, src, y0, ny, xc, sc);
-    if (!combine_) xc.nfields = pres ? 3 : nf;  // (the combine mode forms all six)
-    xfft_backward(xc, sc, phys_, tw_x_, fp64_, s_comp_);
-    if (pres) {
-      XArgs xp = xc;
-      xp.nfields = 1;
-      xp.combine = 0;
-      xp.zero_mean_field = -1;
-      XSrc sp;
-      sp.base = static_cast<const char*>(d_pres_) + (static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
-      sp.nsrc = 1;
-      sp.kx_start[0] = 0;
-      sp.kx_start[1] = p.nkx;
-      xfft_backward(xp, sp, static_cast<char*>(phys_) + 3 * physn_ * esz_, tw_x_, fp64_, s_comp_);
-    }
-    ZRealArgs za;
-    za.NX = p.NX;
-    za.Nzp = p.Nzp;
-    za.nkz = p.nkz;
-    za.ny = ny;
-    za.y0 = y0;
-    za.nfields = nf;
-    za.field_stride = static_cast<long long>(physn_);
-    za.out = nslots ? d_real_ : nullptr;
-    za.out_mask = out_mask;
-    za.out_field_stride = static_cast<long long>(ny * plane);
-    za.moments = d_mom;
-    za.triple = d_triple;
-    za.pres = pres ? 1 : 0;
-    za.pmom = d_pmom;
-    za.U = d_mean_;
-    za.NY = p.NY;
-    zreal(za, phys_, tw_z_, fp64_, s_comp_);
-    if (nslots) {
-      host.resize(static_cast<size_t>(nslots) * ny * plane * tsz);
-      HIP_CHECK(hipMemcpyAsync(host.data(), d_real_, host.size(), hipMemcpyDeviceToHost, s_comp_));
-      HIP_CHECK(hipStreamSynchronize(s_comp_));
-      sink(y0, ny, host.data());
-    }
-  }
-}
-
-// The export passes of a field selection (phys_field_index values): one pass of the six physical-stage
-// fields, or, with p, a pressure-mode pass (u, v, w and Pi, which takes field slot 3) that also serves
-// u, v, w, and a plain pass for any of wx, wy, wz beside it.
-namespace {
-struct ExportPass {
-  unsigned mask = 0;
-  int nf = 0;
-  bool pres = false;
-  // slot of field f (phys_field_index) among this pass's exported fields, -1 if another pass has it
-  int slot(int f) const {
-    const int bit = f == kPresField ? (pres ? 3 : -1) : ((pres && f >= 3) ? -1 : f);
-    if (bit < 0 || !((mask >> bit) & 1u)) return -1;
-    int sl = 0;
-    for (int b = 0; b < bit; ++b) sl += (mask >> b) & 1u;
-    return sl;
-  }
-};
-std::vector<ExportPass> export_passes(const std::vector<int>& fidx) {
-  bool pres = false;
-  unsigned lo = 0, hi = 0;
-  for (int f : fidx) {
-    if (f == kPresField) pres = true;
-    else if (f < 3) lo |= 1u << f;
-    else hi |= 1u << f;
-  }
-  auto top = [](unsigned m) {
-    int n = 0;
-    for (int b = 0; b < 6; ++b)
-      if ((m >> b) & 1u) n = b + 1;
-    return n;
-  };
-  std::vector<ExportPass> out;
-  if (pres) {
-    out.push_back(ExportPass{lo | 8u, 4, true});
-    if (hi) out.push_back(ExportPass{hi, top(hi), false});
-  } else {
-    out.push_back(ExportPass{lo | hi, top(lo | hi), false});
-  }
-  return out;
-}
-}  // namespace
-
-Solver::PhysFields Solver::physical_fields(const std::vector<int>& planes, const std::vector<std::string>& names) {
-  CH_CHECK(!comm_, "physical_fields: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  CH_CHECK(!names.empty() && !planes.empty(), "physical_fields: no fields or no planes requested");
-  std::vector<int> fidx;
-  for (const std::string& nm : names) {
-    const int f = phys_field_index(nm);
-    CH_CHECK(f >= 0, "physical_fields: unknown field '" << nm << "' (u, v, w, wx, wy, wz, p)");
-    fidx.push_back(f);
-  }
-  const std::vector<ExportPass> passes = export_passes(fidx);
-  for (int y : planes) CH_CHECK(y >= 0 && y < p.NY, "physical_fields: plane " << y << " outside [0, NY)");
-  std::vector<int> ys = planes;
-  std::sort(ys.begin(), ys.end());
-  ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
-  PhysFields out;
-  out.planes = planes;
-  out.names = names;
-  out.NX = p.NX;
-  out.Nzp = p.Nzp;
-  const size_t plane = static_cast<size_t>(p.NX) * p.Nzp, np = planes.size();
-  out.data.resize(names.size() * np * plane);
-  // positions of each plane in the request, slot of each field among the exported ones
-  std::vector<std::vector<size_t>> pos(p.NY);
-  for (size_t i = 0; i < np; ++i) pos[planes[i]].push_back(i);
-  for (const ExportPass& ps : passes)
-    export_planes(ys, ps.nf, ps.mask, nullptr, [&](int y0, int ny, const void* h) {
-      for (size_t k = 0; k < names.size(); ++k) {
-        const int sl = ps.slot(fidx[k]);
-        if (sl < 0) continue;
-        for (int y = 0; y < ny; ++y) {
-          const size_t so = (static_cast<size_t>(sl) * ny + y) * plane;
-          for (size_t i : pos[y0 + y]) {
-            double* d = out.data.data() + (k * np + i) * plane;
-            if (fp64_) std::copy(static_cast<const double*>(h) + so, static_cast<const double*>(h) + so + plane, d);
-            else std::copy(static_cast<const float*>(h) + so, static_cast<const float*>(h) + so + plane, d);
-            if (fidx[k] == kPresField) {  // p' = r - <r>_plane, after widening
-              double m = 0.0;
-              for (size_t q = 0; q < plane; ++q) m += d[q];
-              m /= static_cast<double>(plane);
-              for (size_t q = 0; q < plane; ++q) d[q] -= m;
-            }
-          }
-        }
-      }
-    }, nullptr, ps.pres);
-  return out;
-}
-
-std::vector<double> Solver::plane_moments() {
-  CH_CHECK(!comm_, "plane_moments: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  const size_t n = static_cast<size_t>(kMomRows) * p.NY, na = static_cast<size_t>(kMomRows + kTripleRows) * p.NY;
-  if (!d_mom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_mom_), na * sizeof(double)));
-  if (!prepared_) prepare();
-  HIP_CHECK(hipMemsetAsync(d_mom_, 0, n * sizeof(double), s_comp_));
-  std::vector<int> ys(p.NY);
-  for (int j = 0; j < p.NY; ++j) ys[j] = j;
-  export_planes(ys, 3, 0u, d_mom_, nullptr);
-  std::vector<double> m(n);
-  HIP_CHECK(hipMemcpyAsync(m.data(), d_mom_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
-  HIP_CHECK(hipStreamSynchronize(s_comp_));
-  return m;
-}
-
-// the mixed triple products of the turbulent-transport terms: the export stage over every plane
-// with the (w, v) second pair (kernels.hpp ZRealArgs::triple); the moments it forms on the way are
-// dropped
-std::vector<double> Solver::transport_moments() {
-  CH_CHECK(!comm_, "transport_moments: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  const size_t n = static_cast<size_t>(kMomRows) * p.NY, nt = static_cast<size_t>(kTripleRows) * p.NY;
-  if (!d_mom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_mom_), (n + nt) * sizeof(double)));
-  if (!prepared_) prepare();
-  HIP_CHECK(hipMemsetAsync(d_mom_, 0, (n + nt) * sizeof(double), s_comp_));
-  std::vector<int> ys(p.NY);
-  for (int j = 0; j < p.NY; ++j) ys[j] = j;
-  export_planes(ys, 3, 0u, d_mom_, nullptr, d_mom_ + n);
-  std::vector<double> m(nt);
-  HIP_CHECK(hipMemcpyAsync(m.data(), d_mom_ + n, nt * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
-  HIP_CHECK(hipStreamSynchronize(s_comp_));
-  return m;
-}
-
-// ---- pressure ------------------------------------------------------------------------------------
-// The step's transform stage (x-backward, z stage, x-forward; substep index 1: no CFL maxima, no dt
-// update) once more, from K-SPEC's outputs of the current state into d_pres_ instead of over them,
-// then the y-line Poisson solve in place over H_x.  state_ and out_ are only read: the next step sees
-// what it would have seen.  phys_ is scratch between steps, as the export assumes.
-void Solver::pressure_device(double* ms) {
-  CH_CHECK(!comm_, "pressure: the pressure solve is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  if (!prepared_) prepare();
-  if (!d_pres_) {
-    HIP_CHECK(hipMalloc(&d_pres_, 3 * spec_ * esz_));
-    HIP_CHECK(hipMemsetAsync(d_pres_, 0, 3 * spec_ * esz_, s_comp_));
-  }
-  hipEvent_t te[3] = {nullptr, nullptr, nullptr};
-  if (ms) {
-    for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(te[0], s_comp_));
-  }
-  transforms(1, false, d_pres_);
-  if (ms) HIP_CHECK(hipEventRecord(te[1], s_comp_));
-  PressureArgs a;
-  a.N = p.NY;
-  a.lines = p.nkx_loc * nkzs_;
-  a.nkz = nkzs_;
-  a.nkz_real = p.nkz_loc;
-  a.kzb = kzb_;
-  a.kz0 = p.kz0;
-  a.kx0 = p.kx0;
-  a.nkx = p.nkx;
-  a.Kx = p.Kx;
-  a.ax = p.ax;
-  a.az = p.az;
-  a.nu = 1.0 / cfg_.Re;
-  char* h = static_cast<char*>(d_pres_);
-  a.hx = h;
-  a.hy = h + spec_ * esz_;
-  a.hz = h + 2 * spec_ * esz_;
-  a.phi = field_ptr(PHI);
-  a.pi = h;
-  pressure_solve(ytab_, a, fp64_, s_comp_);
-  if (ms) {
-    HIP_CHECK(hipEventRecord(te[2], s_comp_));
-    HIP_CHECK(hipStreamSynchronize(s_comp_));
-    float t01 = 0, t12 = 0;
-    HIP_CHECK(hipEventElapsedTime(&t01, te[0], te[1]));
-    HIP_CHECK(hipEventElapsedTime(&t12, te[1], te[2]));
-    ms[0] = t01;
-    ms[1] = t12;
-    for (hipEvent_t e : te) (void)hipEventDestroy(e);
-  }
-}
-
-std::vector<double> Solver::pressure_timing() {
-  std::vector<double> ms(2, 0.0);
-  pressure_device(ms.data());
-  return ms;
-}
-
-std::vector<std::complex<double>> Solver::pressure_hat() {
-  pressure_device();
-  return spec_to_canonical(d_pres_, "pressure");
-}
-
-// one spectral field on the device (one rank) as canonical [y][kx][kz] complex128 on the host
-std::vector<std::complex<double>> Solver::spec_to_canonical(const void* d_field, const char* what) {
-  const Plan& p = plan_;
-  std::vector<std::complex<double>> t(spec_);
-  if (fp64_) {
-    std::vector<double2> h(spec_);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d_field, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
-    HIP_CHECK(hipStreamSynchronize(s_comp_));
-    for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
-  } else {
-    std::vector<float2> h(spec_);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d_field, spec_ * esz_, hipMemcpyDeviceToHost, s_comp_));
-    HIP_CHECK(hipStreamSynchronize(s_comp_));
-    for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
-  }
-  // device layout -> canonical [y][kx][kz]; what is left behind (padded kz lines and rows of the
-  // blocked layout) must be exactly zero: the x transform of the export reads whole tiles
-  std::vector<std::complex<double>> out(canon_);
-  for (int y = 0; y < p.NY; ++y)
-    for (int i = 0; i < p.nkx_loc; ++i)
-      for (int k = 0; k < p.nkz_loc; ++k) {
-        std::complex<double>& e = t[dev_index(y, i, k)];
-        out[(static_cast<size_t>(y) * p.nkx_loc + i) * p.nkz_loc + k] = e;
-        e = 0.0;
-      }
-  size_t bad = 0;
-  for (size_t i = 0; i < spec_; ++i) bad += (t[i].real() != 0.0 || t[i].imag() != 0.0) ? 1 : 0;
-  CH_CHECK(bad == 0, what << ": " << bad << " padding elements of the spectral layout are not zero");
-  return out;
-}
-
-std::vector<double> Solver::pressure_moments() {
-  CH_CHECK(!comm_, "pressure_moments: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  const size_t N = static_cast<size_t>(p.NY), nm = kMomRows * N, np = kPresRows * N;
-  if (!d_pmom_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pmom_), (nm + np) * sizeof(double)));
-  if (!prepared_) prepare();
-  HIP_CHECK(hipMemsetAsync(d_pmom_, 0, (nm + np) * sizeof(double), s_comp_));
-  std::vector<int> ys(p.NY);
-  for (int j = 0; j < p.NY; ++j) ys[j] = j;
-  // (the moments give <u'>, which is zero to rounding but is subtracted all the same, <v> and <w>
-  // are exactly the mean line's zeros)
-  export_planes(ys, 4, 0u, d_pmom_, nullptr, nullptr, true, d_pmom_ + nm);
-  std::vector<double> h(nm + np);
-  HIP_CHECK(hipMemcpyAsync(h.data(), d_pmom_, (nm + np) * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
-  HIP_CHECK(hipStreamSynchronize(s_comp_));
-  // central moments: <p'p'> = <r^2> - <r>^2, <p'u'> = <r u'> - <r><u'>, <p'v> = <r v>, <p'w> = <r w>
-  std::vector<double> m(4 * N);
-  const double* r = h.data() + nm;
-  for (size_t j = 0; j < N; ++j) {
-    const double rm = r[j], um = h[j];
-    m[j] = r[N + j] - rm * rm;
-    m[N + j] = r[2 * N + j] - rm * um;
-    m[2 * N + j] = r[3 * N + j];
-    m[3 * N + j] = r[4 * N + j];
-  }
-  return m;
-}
-
-// one line of NY values per call and file, as write_stats_files: the pressure r.m.s. and <p'u'>, <p'v>
-void Solver::write_pressure_files() {
-  if (comm_) {
-    if (!pres_note_ && plan_.rank == 0)
-      std::fprintf(stderr, "[channel] pressure_every: PRMS.dat, PU.dat, PV.dat skipped (the pressure solve is single-rank)\n");
-    pres_note_ = true;
-    return;
-  }
-  const std::vector<double> m = pressure_moments();
-  const int N = plan_.NY;
-  auto line = [&](const char* name, const double* v, bool root) {
-    std::ofstream f(cfg_.path + name, std::ios::app);
-    f.precision(8);
-    for (int j = 0; j < N; ++j) f << " " << std::scientific << (root ? std::sqrt(std::max(0.0, v[j])) : v[j]);
-    f << " \n";
-  };
-  line("PRMS.dat", m.data(), true);
-  line("PU.dat", m.data() + N, false);
-  line("PV.dat", m.data() + 2 * N, false);
-}
-
-// ---- spectral static pressure, pressure-strain -------------------------------------------------------
-// The pressure-mode export pass over every plane with the return trip of r (kernels.hpp
-// ZRealArgs::spec_out): per chunk the x-backward of u, v, w and of Pi (into slot 3 of the scratch), the
-// z kernel, which leaves r-hat(x, kz) in slot 3, and the forward x transform of that one field into
-// the chunk's planes of field 1 of d_pres_ (the H_y slot, free after the solve; Pi stays in field 0).
-// The mean line, which holds <r>, is zeroed; the padding of the blocked layout is never written and
-// stays the zeros of the allocation.  Like the export it writes nothing the next step reads.
-void Solver::static_pressure_device() {
-  CH_CHECK(!comm_, "static_pressure: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  pressure_device();
-  const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
-  XArgs xa = x_args();
-  const XSrc src = x_src_local(xa);
-  char* slot3 = static_cast<char*>(phys_) + 3 * physn_ * esz_;
-  char* phat = static_cast<char*>(d_pres_) + spec_ * esz_;
-  for (int y0 = 0; y0 < p.NY; y0 += cap) {
-    const int ny = std::min(cap, p.NY - y0);
-    XArgs xc;
-    XSrc sc;
-    x_chunk(xa, src, y0, ny, xc, sc);
-    if (!combine_) xc.nfields = 3;  // (the combine mode forms all six)
-    xfft_backward(xc, sc, phys_, tw_x_, fp64_, s_comp_);
-    XArgs xp = xc;
-    xp.nfields = 1;
-    xp.combine = 0;
-    xp.zero_mean_field = -1;
-    XSrc sp;
-    const size_t so = static_cast<size_t>(static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
-    sp.base = static_cast<const char*>(d_pres_) + so;
-    sp.nsrc = 1;
-    sp.kx_start[0] = 0;
-    sp.kx_start[1] = p.nkx;
-    xfft_backward(xp, sp, slot3, tw_x_, fp64_, s_comp_);
-    ZRealArgs za;
-    za.NX = p.NX;
-    za.Nzp = p.Nzp;
-    za.nkz = p.nkz;
-    za.ny = ny;
-    za.y0 = y0;
-    za.nfields = 4;
-    za.field_stride = static_cast<long long>(physn_);
-    za.pres = 1;
-    za.spec_out = slot3;
-    za.U = d_mean_;
-    za.NY = p.NY;
-    zreal(za, phys_, tw_z_, fp64_, s_comp_);
-    // (the chunk's planes of the destination, as transforms() addresses them)
-    XDst dc;
-    dc.base = phat + so;
-    dc.ndst = 1;
-    dc.kx_start[0] = 0;
-    dc.kx_start[1] = p.nkx;
-    xfft_forward(xp, slot3, dc, tw_x_, fp64_, s_comp_);
-  }
-  zero_mean_line(phat, p.NY, kzb_, p.nkx_loc * nkzs_, fp64_, s_comp_);
-}
-
-std::vector<std::complex<double>> Solver::static_pressure_hat() {
-  static_pressure_device();
-  return spec_to_canonical(static_cast<const char*>(d_pres_) + spec_ * esz_, "static pressure");
-}
-
-std::vector<double> Solver::pressure_strain() {
-  CH_CHECK(!comm_, "pressure_strain: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  const size_t n = static_cast<size_t>(kPStrainRows) * p.NY;
-  if (!d_pstr_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pstr_), n * sizeof(double)));
-  static_pressure_device();
-  HIP_CHECK(hipMemsetAsync(d_pstr_, 0, n * sizeof(double), s_comp_));
-  PStrainArgs a;
-  a.p = static_cast<const char*>(d_pres_) + spec_ * esz_;
-  if (combine_) {
-    for (int f = 0; f < kCmbIn; ++f) a.f[f] = in_field(f);
-  } else {
-    static const int kSix[4] = {0, 1, 2, 5};  // u, v, w, omega_z
-    for (int f = 0; f < 4; ++f) a.f[f] = in_field(kSix[f]);
-  }
-  a.combine = combine_ ? 1 : 0;
-  a.ax = p.ax;
-  a.az = p.az;
-  a.N = p.NY;
-  a.nkx_loc = p.nkx_loc;
-  a.kx0 = p.kx0;
-  a.nkz_loc = p.nkz_loc;
-  a.kz0 = p.kz0;
-  a.nkzs = nkzs_;
-  a.kzb = kzb_;
-  a.nkx = p.nkx;
-  a.Kx = p.Kx;
-  a.sums = d_pstr_;
-  pstrain_accumulate(a, fp64_, s_comp_);
-  std::vector<double> g(n);
-  HIP_CHECK(hipMemcpyAsync(g.data(), d_pstr_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
-  HIP_CHECK(hipStreamSynchronize(s_comp_));
-  return g;
-}
-
-// one line of NY values per call and file, as write_stats_files: the pressure-strain terms of the uu,
-// vv, ww, uv budgets
-void Solver::write_pstrain_files() {
-  if (comm_) {
-    if (!pstr_note_ && plan_.rank == 0)
-      std::fprintf(stderr, "[channel] pstrain_every: PS_UU.dat, PS_VV.dat, PS_WW.dat, PS_UV.dat skipped (the export is single-rank)\n");
-    pstr_note_ = true;
-    return;
-  }
-  const std::vector<double> m = pressure_strain();
-  const int N = plan_.NY;
-  const char* names[4] = {"PS_UU.dat", "PS_VV.dat", "PS_WW.dat", "PS_UV.dat"};
-  for (int q = 0; q < 4; ++q) {
-    std::ofstream f(cfg_.path + names[q], std::ios::app);
-    f.precision(8);
-    for (int j = 0; j < N; ++j) f << " " << std::scientific << m[static_cast<size_t>(q) * N + j];
-    f << " \n";
-  }
-}
-
-// ---- velocity-gradient sums -----------------------------------------------------------------------
-// As spectra(): K-SPEC's outputs of the current state are read in place, one launch per kx
-// sub-block on the compute stream behind whatever is queued; nothing the next step reads is
-// written, so the step graphs stay valid.
-std::vector<double> Solver::gradient_sums() {
-  const Plan& p = plan_;
-  const size_t n = static_cast<size_t>(kGradRows) * p.NY;
-  if (!d_grad_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_grad_), n * sizeof(double)));
-  if (!prepared_) prepare();
-  HIP_CHECK(hipMemsetAsync(d_grad_, 0, n * sizeof(double), s_comp_));
-  GradSumArgs a;
-  const int nf = bwd_fields();
-  for (int f = 0; f < nf; ++f) a.f[f] = in_field(f);
-  a.combine = combine_ ? 1 : 0;
-  a.ax = p.ax;
-  a.az = p.az;
-  a.N = p.NY;
-  a.nkz_loc = p.nkz_loc;
-  a.kz0 = p.kz0;
-  a.nkzs = nkzs_;
-  a.kzb = kzb_;
-  a.nkx = p.nkx;
-  a.Kx = p.Kx;
-  a.sums = d_grad_;
-  for (int b = 0; b < nkb_; ++b) {
-    GradSumArgs ab = a;
-    for (int f = 0; f < nf; ++f) ab.f[f] = static_cast<const char*>(a.f[f]) + kb_off_[b] * esz_;
-    ab.nkx_loc = kb_cnt_[b];
-    ab.kx0 = p.kx0 + kb_start_[b];
-    gradsum_accumulate(ab, fp64_, s_comp_);
-  }
-  if (comm_) {
-    HIP_CHECK(hipEventRecord(ev_stats_, s_comp_));
-    HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_stats_, 0));
-    comm_->allreduce_sum_f64(d_grad_, n, s_comm_);
-    wait(s_comm_);
-  }
-  std::vector<double> g(n);
-  HIP_CHECK(hipMemcpyAsync(g.data(), d_grad_, n * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
-  wait(s_comp_);
-  return g;
-}
-
-// ---- spectra at every plane -------------------------------------------------------------------------
-// As gradient_sums(): the same fields read in place, one launch per kx sub-block on the compute
-// stream, one all-reduce over both arrays; nothing the next step reads is written.  With the pressure
-// row the device part of static_pressure_hat() runs first (it writes d_pres_ and the step's scratch).
-Solver::PlaneSpectra Solver::plane_spectra(bool pressure) {
-  CH_CHECK(!pressure || !comm_, "plane_spectra: the pressure row is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
-  const size_t nx = static_cast<size_t>(kYSpecRows) * p.NY * (p.Kx + 1), nz = static_cast<size_t>(kYSpecRows) * p.NY * p.nkz;
-  if (!d_yspec_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_yspec_), (nx + nz) * sizeof(double)));
-  if (!h_yspec_) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_yspec_), (nx + nz) * sizeof(double), hipHostMallocDefault));
-  if (!prepared_) prepare();
-  if (pressure) static_pressure_device();
-  HIP_CHECK(hipMemsetAsync(d_yspec_, 0, (nx + nz) * sizeof(double), s_comp_));
-  YSpectraArgs a;
-  const int nf = bwd_fields();
-  for (int f = 0; f < nf; ++f) a.f[f] = in_field(f);
-  if (pressure) a.p = static_cast<const char*>(d_pres_) + spec_ * esz_;
-  a.combine = combine_ ? 1 : 0;
-  a.ax = p.ax;
-  a.az = p.az;
-  a.N = p.NY;
-  a.nkz_loc = p.nkz_loc;
-  a.kz0 = p.kz0;
-  a.nkzs = nkzs_;
-  a.kzb = kzb_;
-  a.nkx = p.nkx;
-  a.Kx = p.Kx;
-  a.nkz = p.nkz;
-  a.ekx = d_yspec_;
-  a.ekz = d_yspec_ + nx;
-  for (int b = 0; b < nkb_; ++b) {
-    YSpectraArgs ab = a;
-    for (int f = 0; f < nf; ++f) ab.f[f] = static_cast<const char*>(a.f[f]) + kb_off_[b] * esz_;
-    if (a.p) ab.p = static_cast<const char*>(a.p) + kb_off_[b] * esz_;
-    ab.nkx_loc = kb_cnt_[b];
-    ab.kx0 = p.kx0 + kb_start_[b];
-    yspectra_accumulate(ab, fp64_, s_comp_);
-  }
-  if (comm_) {
-    HIP_CHECK(hipEventRecord(ev_stats_, s_comp_));
-    HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_stats_, 0));
-    comm_->allreduce_sum_f64(d_yspec_, nx + nz, s_comm_);
-    wait(s_comm_);
-  }
-  PlaneSpectra out;
-  out.rows = {"uu", "vv", "ww", "uv", "wxwx", "wywy", "wzwz", "pp"};
-  // (through pinned memory: a copy into fresh pageable vectors runs at a fraction of the link's rate)
-  HIP_CHECK(hipMemcpyAsync(h_yspec_, d_yspec_, (nx + nz) * sizeof(double), hipMemcpyDeviceToHost, s_comp_));
-  wait(s_comp_);
-  out.ekx.assign(h_yspec_, h_yspec_ + nx);
-  out.ekz.assign(h_yspec_ + nx, h_yspec_ + nx + nz);
-  return out;
-}
-
-namespace {
-// Header of a NumPy v1.0 file: magic, version, little-endian length, the dict padded with spaces to a
-// multiple of 64 bytes in all and newline-terminated.  shape: "(a, b, c)".
-std::string npy_header(const char* descr, const std::string& shape) {
-  std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape + ", }";
-  const size_t hlen = (10 + dict.size() + 1 + 63) / 64 * 64 - 10;
-  dict.resize(hlen - 1, ' ');
-  dict.push_back('\n');
-  std::string h("\x93NUMPY\x01\x00", 8);
-  h.push_back(static_cast<char>(hlen & 0xff));
-  h.push_back(static_cast<char>(hlen >> 8));
-  return h + dict;
-}
-}  // namespace
-
-// <path>YSPEC_KX_<step>.npy (8, NY, Kx+1) and <path>YSPEC_KZ_<step>.npy (8, NY, nkz), float64, and a
-// sidecar <path>YSPEC_<step>.json; every rank takes part in the sums, rank 0 writes
-void Solver::write_yspectra_files() {
-  bool pres = cfg_.yspectra_pressure != 0;
-  if (pres && comm_) {
-    if (!yspec_note_ && plan_.rank == 0)
-      std::fprintf(stderr, "[channel] yspectra_pressure: row pp of YSPEC_*.npy skipped (the pressure solve is single-rank)\n");
-    yspec_note_ = true;
-    pres = false;
-  }
-  const PlaneSpectra sp = plane_spectra(pres);
-  if (plan_.rank != 0) return;
-  const Plan& p = plan_;
-  char step[16];
-  std::snprintf(step, sizeof(step), "%08ld", nstep_);
-  auto put = [&](const char* name, const std::vector<double>& v, int nk) {
-    const std::string fn = cfg_.path + name + step + ".npy";
-    std::ofstream f(fn, std::ios::binary | std::ios::trunc);
-    CH_CHECK(f.good(), "cannot open '" << fn << "'");
-    const std::string h = npy_header("<f8", "(" + std::to_string(kYSpecRows) + ", " + std::to_string(p.NY) + ", " + std::to_string(nk) + ")");
-    f.write(h.data(), static_cast<std::streamsize>(h.size()));
-    f.write(reinterpret_cast<const char*>(v.data()), static_cast<std::streamsize>(v.size() * sizeof(double)));
-    f.close();
-    CH_CHECK(!f.fail(), "writing '" << fn << "' failed");
-  };
-  put("YSPEC_KX_", sp.ekx, p.Kx + 1);
-  put("YSPEC_KZ_", sp.ekz, p.nkz);
-  double hv[2];
-  HIP_CHECK(hipMemcpy(hv, d_dt_, sizeof(hv), hipMemcpyDeviceToHost));
-  std::ofstream js(cfg_.path + "YSPEC_" + step + ".json");
-  js.precision(17);
-  js << "{\"step\": " << nstep_ << ", \"time\": " << hv[1] << ", \"rows\": [";
-  for (size_t k = 0; k < sp.rows.size(); ++k) js << (k ? ", " : "") << "\"" << sp.rows[k] << "\"";
-  js << "], \"pressure\": " << (pres ? "true" : "false") << ", \"ax\": " << p.ax << ", \"az\": " << p.az << ", \"y\": [";
-  for (int j = 0; j < p.NY; ++j) js << (j ? ", " : "") << grid_.y[j];
-  js << "], \"Re\": " << cfg_.Re << "}\n";
-}
-
-// one line of NY values per call and file, as write_stats_files: the vorticity r.m.s., the
-// dissipation 2 nu g of the uu, vv, ww, uv budgets and (one rank without a communicator) the triple
-// products of the turbulent transport
-void Solver::write_budget_files() {
-  const std::vector<double> g = gradient_sums();
-  std::vector<double> t;
-  if (!comm_) {
-    t = transport_moments();
-  } else if (!budget_note_ && plan_.rank == 0) {
-    std::fprintf(stderr, "[channel] budget_every: TRIPLE_*.dat skipped (the physical-space export is single-rank)\n");
-    budget_note_ = true;
-  }
-  if (plan_.rank != 0) return;
-  const int N = plan_.NY;
-  const double nu = 1.0 / cfg_.Re;
-  auto line = [&](const char* name, const double* v, double scale, bool root) {
-    std::ofstream f(cfg_.path + name, std::ios::app);
-    f.precision(8);
-    for (int j = 0; j < N; ++j) f << " " << std::scientific << (root ? std::sqrt(std::max(0.0, v[j])) : scale * v[j]);
-    f << " \n";
-  };
-  const char* wn[3] = {"WXRMS.dat", "WYRMS.dat", "WZRMS.dat"};
-  const char* en[4] = {"EPS_UU.dat", "EPS_VV.dat", "EPS_WW.dat", "EPS_UV.dat"};
-  const char* tn[3] = {"TRIPLE_UUV.dat", "TRIPLE_WWV.dat", "TRIPLE_UVV.dat"};
-  for (int q = 0; q < 3; ++q) line(wn[q], g.data() + q * N, 1.0, true);
-  for (int q = 0; q < 4; ++q) line(en[q], g.data() + (3 + q) * N, 2.0 * nu, false);
-  if (!t.empty())
-    for (int q = 0; q < 3; ++q) line(tn[q], t.data() + q * N, 1.0, false);
-}
-
-// One NumPy v1.0 file per field, <path>FIELD_<name>_<step>.npy of shape (nplanes, NX, Nzp) in the
-// storage precision, and a sidecar <path>FIELDS_<step>.json
-void Solver::write_field_files() {
-  const Plan& p = plan_;
-  const std::vector<int> planes = cfg_.fields_plane_list();
-  const std::vector<std::string> names = cfg_.fields_list();
-  std::vector<int> ys = planes;
-  std::sort(ys.begin(), ys.end());
-  ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
-  std::vector<int> fidx;
-  for (const std::string& nm : names) fidx.push_back(phys_field_index(nm));
-  const std::vector<ExportPass> passes = export_passes(fidx);
-  char step[16];
-  std::snprintf(step, sizeof(step), "%08ld", nstep_);
-  const size_t tsz = fp64_ ? sizeof(double) : sizeof(float);
-  const size_t plane = static_cast<size_t>(p.NX) * p.Nzp;
-  const std::string head = npy_header(fp64_ ? "<f8" : "<f4", "(" + std::to_string(planes.size()) + ", " + std::to_string(p.NX) +
-                                                                 ", " + std::to_string(p.Nzp) + ")");
-  std::vector<std::ofstream> files;
-  for (const std::string& nm : names) {
-    files.emplace_back(cfg_.path + "FIELD_" + nm + "_" + step + ".npy", std::ios::binary | std::ios::trunc);
-    std::ofstream& f = files.back();
-    CH_CHECK(f.good(), "cannot open field file for '" << nm << "' under '" << cfg_.path << "'");
-    f.write(head.data(), static_cast<std::streamsize>(head.size()));
-  }
-  const std::streamoff data0 = static_cast<std::streamoff>(head.size());
-  std::vector<std::vector<size_t>> pos(p.NY);
-  for (size_t i = 0; i < planes.size(); ++i) pos[planes[i]].push_back(i);
-  std::vector<char> pbuf;
-  for (const ExportPass& ps : passes)
-    export_planes(ys, ps.nf, ps.mask, nullptr, [&](int y0, int ny, const void* h) {
-      for (size_t k = 0; k < names.size(); ++k) {
-        const int sl = ps.slot(fidx[k]);
-        if (sl < 0) continue;
-        for (int y = 0; y < ny; ++y) {
-          const size_t so = (static_cast<size_t>(sl) * ny + y) * plane * tsz;
-          const char* src = static_cast<const char*>(h) + so;
-          if (fidx[k] == kPresField) {  // p' = r - <r>_plane (the mean formed in double)
-            pbuf.assign(src, src + plane * tsz);
-            double m = 0.0;
-            if (fp64_) {
-              double* q = reinterpret_cast<double*>(pbuf.data());
-              for (size_t e = 0; e < plane; ++e) m += q[e];
-              m /= static_cast<double>(plane);
-              for (size_t e = 0; e < plane; ++e) q[e] -= m;
-            } else {
-              float* q = reinterpret_cast<float*>(pbuf.data());
-              for (size_t e = 0; e < plane; ++e) m += q[e];
-              m /= static_cast<double>(plane);
-              for (size_t e = 0; e < plane; ++e) q[e] = static_cast<float>(q[e] - m);
-            }
-            src = pbuf.data();
-          }
-          for (size_t i : pos[y0 + y]) {
-            files[k].seekp(data0 + static_cast<std::streamoff>(i * plane * tsz));
-            files[k].write(src, static_cast<std::streamsize>(plane * tsz));
-          }
-        }
-      }
-    }, nullptr, ps.pres);
-  for (size_t k = 0; k < names.size(); ++k) {
-    files[k].close();
-    CH_CHECK(!files[k].fail(), "writing the field file of '" << names[k] << "' failed");
-  }
-  double hv[2];
-  HIP_CHECK(hipMemcpy(hv, d_dt_, sizeof(hv), hipMemcpyDeviceToHost));
-  std::ofstream js(cfg_.path + "FIELDS_" + step + ".json");
-  js.precision(17);
-  js << "{\"step\": " << nstep_ << ", \"time\": " << hv[1] << ", \"planes\": [";
-  for (size_t i = 0; i < planes.size(); ++i) js << (i ? ", " : "") << planes[i];
-  js << "], \"y\": [";
-  for (size_t i = 0; i < planes.size(); ++i) js << (i ? ", " : "") << grid_.y[planes[i]];
-  js << "], \"fields\": [";
-  for (size_t k = 0; k < names.size(); ++k) js << (k ? ", " : "") << "\"" << names[k] << "\"";
-  js << "], \"NX\": " << p.NX << ", \"Nzp\": " << p.Nzp << ", \"LX\": " << cfg_.LX << ", \"LZ\": " << cfg_.LZ << "}\n";
-}
-
-// skewness m3 / m2^1.5 and flatness m4 / m2^2 of u, v, w per plane (0 where m2 = 0: the walls), one
-// line of NY values per call, as write_stats_files
-void Solver::write_moment_files(const std::vector<double>& m) {
-  const int N = plan_.NY;
-  auto app = [&](const char* name) { return std::ofstream(cfg_.path + name, std::ios::app); };
-  const char* sk[3] = {"USKEW.dat", "VSKEW.dat", "WSKEW.dat"};
-  const char* fl[3] = {"UFLAT.dat", "VFLAT.dat", "WFLAT.dat"};
-  const int r2[3] = {1, 2, 3}, r3[3] = {5, 6, 7}, r4[3] = {8, 9, 10};
-  for (int q = 0; q < 3; ++q) {
-    auto fs = app(sk[q]);
-    auto ff = app(fl[q]);
-    for (int j = 0; j < N; ++j) {
-      const double m2 = m[r2[q] * N + j];
-      const double d3 = m2 > 0 ? m2 * std::sqrt(m2) : 0.0, d4 = m2 * m2;  // (either may underflow to 0)
-      fs << " " << std::fixed << (d3 > 0 ? m[r3[q] * N + j] / d3 : 0.0);
-      ff << " " << std::fixed << (d4 > 0 ? m[r4[q] * N + j] / d4 : 0.0);
-    }
-    fs << " \n";
-    ff << " \n";
-  }
-}
-
 void Solver::write_json(const StepLog& L, double ms_per_step) {
   if (plan_.rank != 0 || cfg_.log_json.empty()) return;
   std::ofstream f(cfg_.log_json, std::ios::app);

@@ -358,6 +358,20 @@ struct SpectraArgs {
 };
 // accumulates (+=) into ekx/ekz; map is overwritten for the local block
 void spectra_accumulate(const SpectraArgs& a, bool fp64, hipStream_t s);
+// What the three all-plane reductions below read: one local block of spectral fields, walked once.
+struct SpecWalkArgs {
+  // six-output mode: u, v, w, omega_x, omega_y (the omega state), omega_z; combine mode: D1 v, v,
+  // D1 omega, omega, phi (f[5] unused), from which u, w, omega_x, omega_z are formed per element.
+  // A reduction needs only the fields its rows use.
+  const void* f[6] = {};
+  const void* p = nullptr;            // p-hat' in the layout of the fields (pressure strain; optional for the spectra)
+  int combine = 0;
+  double ax = 1.0, az = 2.0;
+  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
+  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
+  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
+  int nkx = 0, Kx = 0;                // global retained kx count
+};
 // Velocity-gradient plane sums of the current state (vorticity r.m.s., dissipation): every plane of
 // one local block of spectral fields is read once and kGradRows Parseval sums per plane are
 // accumulated (+=) into sums[kGradRows][N].  Weights as SpectraArgs (kz = 0 once, kz > 0 twice, the
@@ -365,16 +379,7 @@ void spectra_accumulate(const SpectraArgs& a, bool fp64, hipStream_t s);
 // D w = omega_x + i be v, D v = -i (al u + be w), so no y-solve is needed.  Rows: |omega_x|^2,
 // |omega_y|^2, |omega_z|^2, g_uu = k2 |u|^2 + |D u|^2, g_vv, g_ww, g_uv = k2 Re(u v*) + Re(Du Dv*).
 constexpr int kGradRows = 7;
-struct GradSumArgs {
-  // six-output mode: u, v, w, omega_x, omega_y (the omega state), omega_z; combine mode: D1 v, v,
-  // D1 omega, omega, phi (f[5] unused), from which u, w, omega_x, omega_z are formed per element
-  const void* f[6] = {};
-  int combine = 0;
-  double ax = 1.0, az = 2.0;
-  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
-  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
-  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
-  int nkx = 0, Kx = 0;                // global retained kx count
+struct GradSumArgs : SpecWalkArgs {   // all six fields (p unused)
   double* sums = nullptr;             // [kGradRows][N]
 };
 void gradsum_accumulate(const GradSumArgs& a, bool fp64, hipStream_t s);
@@ -386,17 +391,7 @@ void gradsum_accumulate(const GradSumArgs& a, bool fp64, hipStream_t s);
 //   ps_uu = 2 Re<p (i al u)*>, ps_vv = 2 Re<p (D v)*>, ps_ww = 2 Re<p (i be w)*>,
 //   ps_uv = Re<p (D u + i al v)*>, pu = Re<p u*>, pv = Re<p v*>, pp_band = <|p|^2>.
 constexpr int kPStrainRows = 7;
-struct PStrainArgs {
-  const void* p = nullptr;            // p-hat, in the layout of the fields
-  // six-output mode: u, v, w, omega_z (f[4] unused); combine mode: D1 v, v, D1 omega, omega, phi, from
-  // which u, w, omega_z are formed per element
-  const void* f[5] = {};
-  int combine = 0;
-  double ax = 1.0, az = 2.0;
-  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
-  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
-  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
-  int nkx = 0, Kx = 0;                // global retained kx count
+struct PStrainArgs : SpecWalkArgs {   // p and, in six-output mode, only u, v, w, omega_z (f[3], f[4] unused)
   double* sums = nullptr;             // [kPStrainRows][N]
 };
 void pstrain_accumulate(const PStrainArgs& a, bool fp64, hipStream_t s);
@@ -407,16 +402,8 @@ void pstrain_accumulate(const PStrainArgs& a, bool fp64, hipStream_t s);
 // Summing either output over its wavenumber gives the plane mean of the product.  Rows: |u|^2, |v|^2,
 // |w|^2, Re(u v*), |omega_x|^2, |omega_y|^2, |omega_z|^2, |p|^2 (left untouched when p is null).
 constexpr int kYSpecRows = 8;
-struct YSpectraArgs {
-  // as GradSumArgs: u, v, w, omega_x, omega_y, omega_z, or the five combine inputs
-  const void* f[6] = {};
-  const void* p = nullptr;            // p-hat' in the layout of the fields, or null
-  int combine = 0;
-  double ax = 1.0, az = 2.0;
-  int N = 0;                          // NY (rows beyond it, the blocked layout's padding, are skipped)
-  int nkx_loc = 0, kx0 = 0, nkz_loc = 0, kz0 = 0;
-  int nkzs = 0, kzb = 0;              // line stride in kz (lines past nkz_loc are skipped), layout (spec_index)
-  int nkx = 0, Kx = 0, nkz = 0;       // global retained counts
+struct YSpectraArgs : SpecWalkArgs {  // all six fields; p or null
+  int nkz = 0;                        // global retained kz count
   double* ekx = nullptr;              // [kYSpecRows][N][Kx + 1]
   double* ekz = nullptr;              // [kYSpecRows][N][nkz]
 };

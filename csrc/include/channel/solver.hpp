@@ -257,6 +257,20 @@ class Solver {
   void export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
                      const std::function<void(int, int, const void*)>& sink, double* d_triple = nullptr,
                      bool pres = false, double* d_pmom = nullptr);
+  // what the diagnostics share (diagnostics.cpp): the arguments of the all-plane spectral reductions
+  // for the whole local slab (the fields of the mask `six`, p-hat' on request); fn(byte offset, kx count,
+  // global kx start) per kx sub-block; the all-reduce (any communicator) and host copy of n accumulated
+  // doubles; the list of all planes; the pressure-mode x-backward of Pi into slot 3 of the scratch and
+  // the common z export arguments of a chunk; the export passes of a field selection, plane by plane
+  void walk_args(SpecWalkArgs& a, unsigned six, bool pres) const;
+  template <typename F>
+  void for_kblocks(F&& fn) const;
+  void reduce_fetch(double* d, size_t n, double* h);
+  std::vector<int> all_planes() const;
+  XArgs pi_backward(const XArgs& xc, const XSrc& sc);
+  ZRealArgs zreal_args(int y0, int ny, int nf) const;
+  template <typename Put>
+  void export_fields(const std::vector<int>& planes, const std::vector<int>& fidx, Put&& put);
   void write_json(const StepLog& L, double ms_per_step);
   void wait(hipStream_t s);           // stream sync with the communicator watchdog (P > 1)
   void invalidate_graphs();

@@ -133,6 +133,21 @@ void kz0_symmetrize_dist(void* q, const void* col_all, const Kz0SymArgs& a, bool
   HIP_LAUNCH_CHECK(s);
 }
 
+// the mean line (local kx 0, kz 0) of every plane of one spectral field becomes zero
+template <typename T2>
+__global__ void __launch_bounds__(64) zero_mean_line_kernel(T2* q, int N, int kzb, int lines) {
+  const int y = blockIdx.x * 64 + threadIdx.x;
+  if (y < N) q[spec_row_off(kzb, lines, y)] = T2{0, 0};
+}
+
+void zero_mean_line(void* q, int N, int kzb, int lines, bool fp64, hipStream_t s) {
+  CH_CHECK(q && N > 0 && lines > 0, "zero_mean_line: empty");
+  const dim3 grid(static_cast<unsigned>((N + 63) / 64));
+  if (fp64) hipLaunchKernelGGL((zero_mean_line_kernel<double2>), grid, dim3(64), 0, s, static_cast<double2*>(q), N, kzb, lines);
+  else hipLaunchKernelGGL((zero_mean_line_kernel<float2>), grid, dim3(64), 0, s, static_cast<float2*>(q), N, kzb, lines);
+  HIP_LAUNCH_CHECK(s);
+}
+
 // Energy spectra of u, v, w at selected y planes (the reference's calcSpectra, statistics.cu:245-326,
 // is dead code that dumped |q|^2 of one plane; here it is a live, device-side diagnostic).
 // One block per (local kx, plane); fluctuations only (the (0,0) line carries U(y)).  The kz = 0

@@ -15,35 +15,20 @@
 // Both sets leave the block through LDS as contiguous runs: one atomicAdd per (row, plane, bin) and
 // block, consecutive lanes on consecutive bins.  Padded planes (y >= N) and lines past the line
 // stride are not loaded; padded kz lines (kl >= nkz_loc) are loaded with their piece and masked.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "channel/common.hpp"
-#include "channel/kernels.hpp"
+#include "specwalk.hpp"
 
 namespace channel {
 
 namespace {
 
-constexpr int kYsNT = 256;        // threads per block
-constexpr int kYsBlocks = 2048;   // blocks per launch aimed at (8 per CU), as the gradient sums
+using namespace specwalk;
+constexpr int kYsNT = kNT, kYsBlocks = kBlocks;  // threads per block, blocks per launch aimed at, as the gradient sums
 // kx rows per block: at most kYsKxMax (the LDS accumulators: one per bin, plane and row), at least
 // kYsKxMin where there are as many (the kz sums leave a block once, 8 atomics per element, whatever
 // the number of rows it has read)
 constexpr int kYsKxMax = 64, kYsKxMin = 8;
 constexpr int kYsSlots = 64;      // (plane of the chunk, row) pairs
 constexpr int kYsLds = kYsKxMax * (kYsSlots + 1);  // doubles; also holds the kz sums, [slot][lines + 1]
-
-template <typename T2, int V>
-struct alignas(sizeof(T2) * V) YsVec {
-  T2 c[V];
-};
-
-struct YsC {
-  double x, y;
-};
-__device__ __forceinline__ double ys_sq(YsC a) { return a.x * a.x + a.y * a.y; }
 
 // Sum of t[q] over the 8 lanes that differ in the lane bits M0, M1, M2: the lane with bits (b0, b1,
 // b2) returns row 4 b0 + 2 b1 + b2.
@@ -66,12 +51,11 @@ __global__ void __launch_bounds__(kYsNT) yspectra_kernel(YSpectraArgs a, int kxs
   constexpr int NS = TILED ? kYsSlots : kYSpecRows;          // slots in use
   static_assert(kYSpecRows == 8 && kSpecYBlock * kYSpecRows == kYsSlots, "slots are (plane of the chunk, row)");
   static_assert(NS * (ZL + 1) <= kYsLds, "the kz sums are staged in the accumulators' LDS");
-  using Vec = YsVec<T2, V>;
   __shared__ double acc[kYsLds];
   const int tid = threadIdx.x, lane = tid & 63;
   const int zs = blockIdx.x, rg = blockIdx.y;
   // this lane's plane of the chunk and first line of the slice; the element offset in a kx row
-  const int yy = TILED ? ((tid * V) >> 3) & 7 : 0;
+  const int yy = plane_of<V, TILED>(tid);
   const int kll = TILED ? (((tid * V) >> 6) << 3) | ((tid * V) & 7) : tid;
   const int kl0 = zs * ZL + kll;
   const int y = TILED ? rg * kSpecYBlock + yy : rg;
@@ -86,7 +70,7 @@ __global__ void __launch_bounds__(kYsNT) yspectra_kernel(YSpectraArgs a, int kxs
   const int amin = min(ys_akx(a, g0), ys_akx(a, g1));
   const int amax = straddle ? max(a.Kx, a.nkx - a.Kx - 1) : max(ys_akx(a, g0), ys_akx(a, g1));
   const int nb = amax - amin + 1;  // <= i1 - i0 <= kYsKxMax
-  const int nf = a.combine ? 5 : 6;
+  const unsigned need = inputs(a, kAll);
   const bool hasp = a.p != nullptr;
   for (int i = tid; i < nb * (kYsSlots + 1); i += kYsNT) acc[i] = 0.0;
   __syncthreads();
@@ -97,54 +81,34 @@ __global__ void __launch_bounds__(kYsNT) yspectra_kernel(YSpectraArgs a, int kxs
     for (int q = 0; q < kYSpecRows; ++q) s[u][q] = 0.0;
   for (int i = i0; i < i1; ++i) {
     const int ig = a.kx0 + i;
-    const int kx = ig <= a.Kx ? ig : ig - a.nkx;
+    const int kx = signed_kx(a, i);
     double t[kYSpecRows];
 #pragma unroll
     for (int q = 0; q < kYSpecRows; ++q) t[q] = 0.0;
     if (live) {
-      const size_t e = base + static_cast<size_t>(i) * rowlen + eoff;
-      Vec v[6], vp;
+      const size_t rb = base + static_cast<size_t>(i) * rowlen;
+      Vec<T2, V> v[6], vp;
 #pragma unroll
       for (int f = 0; f < 6; ++f)
-        if (f < nf) v[f] = *reinterpret_cast<const Vec*>(static_cast<const T2*>(a.f[f]) + e);
-      if (hasp) vp = *reinterpret_cast<const Vec*>(static_cast<const T2*>(a.p) + e);
+        if ((need >> f) & 1u) v[f] = load<T2, V>(a.f[f], rb, eoff);
+      if (hasp) vp = load<T2, V>(a.p, rb, eoff);
       const double al = a.ax * kx;
 #pragma unroll
       for (int u = 0; u < V; ++u) {
         const int kl = kl0 + u, kz = a.kz0 + kl;
         if (kl >= a.nkz_loc || (kx == 0 && kz == 0)) continue;
-        const double wgt = kz == 0 ? 1.0 : 2.0;
-        const double be = a.az * kz;
-        YsC cu, cv, cw, ox, oy, oz;
-        cv = YsC{static_cast<double>(v[1].c[u].x), static_cast<double>(v[1].c[u].y)};
-        if (a.combine) {
-          // u = i (al D1v - be om) / k2, w = i (be D1v + al om) / k2, omega_x = i (be phi + al D1om) / k2,
-          // omega_z = i (be D1om - al phi) / k2 (COMPAT.md "combine mode"; fft_impl.hpp cmb_pair)
-          const double r = 1.0 / (al * al + be * be);
-          const YsC d{static_cast<double>(v[0].c[u].x), static_cast<double>(v[0].c[u].y)};
-          const YsC dom{static_cast<double>(v[2].c[u].x), static_cast<double>(v[2].c[u].y)};
-          const YsC ph{static_cast<double>(v[4].c[u].x), static_cast<double>(v[4].c[u].y)};
-          oy = YsC{static_cast<double>(v[3].c[u].x), static_cast<double>(v[3].c[u].y)};
-          cu = YsC{-(al * d.y - be * oy.y) * r, (al * d.x - be * oy.x) * r};
-          cw = YsC{-(be * d.y + al * oy.y) * r, (be * d.x + al * oy.x) * r};
-          ox = YsC{-(be * ph.y + al * dom.y) * r, (be * ph.x + al * dom.x) * r};
-          oz = YsC{-(be * dom.y - al * ph.y) * r, (be * dom.x - al * ph.x) * r};
-        } else {
-          cu = YsC{static_cast<double>(v[0].c[u].x), static_cast<double>(v[0].c[u].y)};
-          cw = YsC{static_cast<double>(v[2].c[u].x), static_cast<double>(v[2].c[u].y)};
-          ox = YsC{static_cast<double>(v[3].c[u].x), static_cast<double>(v[3].c[u].y)};
-          oy = YsC{static_cast<double>(v[4].c[u].x), static_cast<double>(v[4].c[u].y)};
-          oz = YsC{static_cast<double>(v[5].c[u].x), static_cast<double>(v[5].c[u].y)};
-        }
+        const double be = mode_of(a, kz).be, wgt = mode_of(a, kz).wgt;
+        Comp m;
+        components<kAll>(m, v, u, a.combine, al, be);
         double c[kYSpecRows];
-        c[0] = wgt * ys_sq(cu);
-        c[1] = wgt * ys_sq(cv);
-        c[2] = wgt * ys_sq(cw);
-        c[3] = wgt * (cu.x * cv.x + cu.y * cv.y);
-        c[4] = wgt * ys_sq(ox);
-        c[5] = wgt * ys_sq(oy);
-        c[6] = wgt * ys_sq(oz);
-        c[7] = hasp ? wgt * ys_sq(YsC{static_cast<double>(vp.c[u].x), static_cast<double>(vp.c[u].y)}) : 0.0;
+        c[0] = wgt * sq(m.u);
+        c[1] = wgt * sq(m.v);
+        c[2] = wgt * sq(m.w);
+        c[3] = wgt * (m.u.x * m.v.x + m.u.y * m.v.y);
+        c[4] = wgt * sq(m.ox);
+        c[5] = wgt * sq(m.oy);
+        c[6] = wgt * sq(m.oz);
+        c[7] = hasp ? wgt * sq(widen(vp.c[u])) : 0.0;
 #pragma unroll
         for (int q = 0; q < kYSpecRows; ++q) {
           s[u][q] += c[q];
@@ -152,21 +116,14 @@ __global__ void __launch_bounds__(kYsNT) yspectra_kernel(YSpectraArgs a, int kxs
         }
       }
     }
-    // the lanes of one plane: all 64 (plain); lane bits 3..5 select the plane with one element per
-    // lane, bits 2..4 with two
-    double x;
-    int q;
+    // over the lanes of the plane (specwalk.hpp: they differ in bits 1, 2, kLaneBit2, and in the plain
+    // layout in the upper bits too)
+    constexpr int B2 = kLaneBit2<V, TILED>;
+    double x = ys_reduce_scatter<1, 2, B2>(t, lane);
+    const int q = (lane & 1) << 2 | (lane & 2) | ((lane & B2) ? 1 : 0);
     if (!TILED) {
-      x = ys_reduce_scatter<1, 2, 4>(t, lane);
-      q = (lane & 1) << 2 | (lane & 2) | (lane & 4) >> 2;
 #pragma unroll
       for (int o = 8; o <= 32; o <<= 1) x += __shfl_xor(x, o);
-    } else if (V == 2) {
-      x = ys_reduce_scatter<1, 2, 32>(t, lane);
-      q = (lane & 1) << 2 | (lane & 2) | (lane & 32) >> 5;
-    } else {
-      x = ys_reduce_scatter<1, 2, 4>(t, lane);
-      q = (lane & 1) << 2 | (lane & 2) | (lane & 4) >> 2;
     }
     if (TILED || (lane >> 3) == 0) atomicAdd(&acc[(ys_akx(a, ig) - amin) * (kYsSlots + 1) + yy * kYSpecRows + q], x);
   }
@@ -217,26 +174,12 @@ void yspectra_launch(const YSpectraArgs& a, hipStream_t s) {
 }  // namespace
 
 void yspectra_accumulate(const YSpectraArgs& a, bool fp64, hipStream_t s) {
-  CH_CHECK(a.N > 0 && a.nkx_loc > 0 && a.nkz_loc > 0 && a.nkzs >= a.nkz_loc && a.ekx && a.ekz, "yspectra: empty");
-  CH_CHECK(a.kzb == 0 || (a.kzb == kSpecKzBlock && a.nkzs % kSpecKzBlock == 0), "yspectra: bad spectral layout");
-  CH_CHECK(a.N <= 65535, "yspectra: too many planes");
   CH_CHECK(a.Kx >= 0 && a.nkx == 2 * a.Kx + 1 && a.kx0 >= 0 && a.kx0 + a.nkx_loc <= a.nkx, "yspectra: bad kx range");
   CH_CHECK(a.kz0 >= 0 && a.kz0 + a.nkz_loc <= a.nkz, "yspectra: bad kz range");
-  const int nf = a.combine ? 5 : 6;
-  bool al16 = !a.p || reinterpret_cast<uintptr_t>(a.p) % 16 == 0;
-  for (int f = 0; f < nf; ++f) {
-    CH_CHECK(a.f[f], "yspectra: missing field " << f);
-    al16 = al16 && reinterpret_cast<uintptr_t>(a.f[f]) % 16 == 0;
-  }
-  if (a.kzb) {
-    if (fp64) yspectra_launch<double2, 1, true>(a, s);
-    else if (al16) yspectra_launch<float2, 2, true>(a, s);
-    else yspectra_launch<float2, 1, true>(a, s);
-  } else {
-    if (fp64) yspectra_launch<double2, 1, false>(a, s);
-    else yspectra_launch<float2, 1, false>(a, s);
-  }
-  HIP_LAUNCH_CHECK(s);
+  dispatch(a, fp64, kAll, a.ekx && a.ekz, "yspectra", s, [&](auto i) {
+    using I = decltype(i);
+    yspectra_launch<typename I::T2, I::V, I::TILED>(a, s);
+  });
 }
 
 }  // namespace channel
