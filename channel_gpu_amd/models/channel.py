@@ -11,6 +11,7 @@ RCCL id (``parallel.bootstrap``); otherwise the torch-free native TCP rendezvous
 """
 from __future__ import annotations
 
+import math
 import sys
 
 import numpy as np
@@ -173,10 +174,39 @@ class ChannelFlow:
         d["kz"] = 2.0 * np.pi / self.cfg.LZ * np.arange(d["ekz"].shape[-1])
         return d
 
+    def plane_histograms(self, planes=None, nbins: int = 128, njoint: int = 64, span: float = 8.0,
+                         vorticity: bool = False, centre=None, halfwidth=None) -> dict:
+        """Histograms of u, v, w (``vorticity``: and wx, wy, wz) of the current state at the distinct y
+        indices ``planes`` (default: every plane), the joint histogram of (u, v) and the quadrant split
+        of u'v, formed on the device by the export stage (``reference.pdfs`` has the binning rule):
+        ``hist`` ``(nhf, np, nbins + 2)`` and ``joint`` ``(np, njoint + 2, njoint + 2)``, uint64 with
+        the under- and overflow bins first and last; ``quad`` ``(8, np)``, the plane means of u'v over
+        Q1 .. Q4 and the quadrants' sample fractions; ``centre`` and ``halfwidth`` ``(nhf, np)`` as used
+        (given, or U(y) for u, -dU/dy for wz, 0 otherwise and ``span`` times the plane r.m.s. of the
+        current state); ``names``, ``planes``, ``y`` and the bin ``edges`` in units of the half-width.
+        One rank without a communicator; the run is not disturbed."""
+        if planes is None:
+            planes = range(self.cfg.NY)
+        planes = [int(j) for j in planes]
+        flat = lambda a: [] if a is None else [float(v) for v in np.asarray(a, float).reshape(-1)]  # noqa: E731
+        nhf = 6 if vorticity else 3
+        for a, what in ((centre, "centre"), (halfwidth, "halfwidth")):
+            if a is not None and np.asarray(a).shape != (nhf, len(planes)):
+                raise ValueError(f"{what} must have shape ({nhf}, {len(planes)})")
+        d = dict(self.solver.plane_histograms(planes, int(nbins), int(njoint), float(span), bool(vorticity),
+                                              flat(centre), flat(halfwidth)))
+        for k in ("hist", "joint", "quad", "centre", "halfwidth"):
+            d[k] = np.asarray(d[k])
+        d["names"], d["planes"] = list(d["names"]), list(d["planes"])
+        d["y"] = self.y[planes]
+        d["edges"] = np.linspace(-1.0, 1.0, int(nbins) + 1)
+        return d
+
     # ---- time-averaged statistics -------------------------------------------------------------
     def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False,
                           pressure: bool = False, pressure_strain: bool = False, spectra: bool = False,
-                          spectra_pressure: bool = False):
+                          spectra_pressure: bool = False, pdfs: bool = False, pdf_planes=None, pdf_bins: int = 128,
+                          pdf_span: float = 8.0, pdf_vorticity: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
         ``moments``: also the third and fourth central moments (skewness / flatness profiles);
@@ -186,7 +216,11 @@ class ChannelFlow:
         ``pressure_strain``: also the pressure-strain terms (with ``budgets`` and ``pressure`` the
         per-component budgets then close: ``closure_uu``, ``closure_vv``, ``closure_ww``, ``closure_uv``);
         ``spectra``: also the 1-D spectra at every plane (``TurbulenceStatistics.spectra``; any number
-        of ranks), with row ``pp`` when ``spectra_pressure`` (one rank)."""
+        of ranks), with row ``pp`` when ``spectra_pressure`` (one rank);
+        ``pdfs``: also the histograms at ``pdf_planes`` (default: every plane) with ``pdf_bins`` bins over
+        ``pdf_span`` r.m.s. either side, with the vorticity when ``pdf_vorticity``
+        (``TurbulenceStatistics.pdfs``; one rank).  The first sample's centres and half-widths bin every
+        later sample."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -209,6 +243,10 @@ class ChannelFlow:
                 if spectra:
                     sp = self.plane_spectra(spectra_pressure)
                     self.statistics.add_spectra(sp["ekx"], sp["ekz"], sp["kx"], sp["kz"], self.cfg.NX, 2 * self.cfg.NZ - 2)
+                if pdfs:
+                    c, hw = self.statistics.pdf_frozen() or (None, None)
+                    self.statistics.add_histograms(self.plane_histograms(pdf_planes, pdf_bins, math.gcd(int(pdf_bins), 64),
+                                                                         pdf_span, pdf_vorticity, c, hw))
         return self.statistics
 
     def grid_points(self) -> int:

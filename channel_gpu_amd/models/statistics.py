@@ -16,7 +16,8 @@ pressure-velocity correlations and the pressure-diffusion terms of those budgets
 sums of the spectral static pressure (``Solver.pressure_strain``) into the pressure-strain terms, with
 which the uu, vv, ww and uv budgets close component by component.  The one-dimensional spectra at
 every plane (``Solver.plane_spectra``) are averaged into wall-unit spectra, premultiplied spectra and
-two-point correlations (``spectra``).
+two-point correlations (``spectra``).  The per-plane histograms (``Solver.plane_histograms``) are summed
+into PDFs, the joint PDF of (u', v) and the quadrant split of -u'v' (``pdfs``).
 """
 from __future__ import annotations
 
@@ -72,6 +73,95 @@ class TurbulenceStatistics:
         self.nsp = 0
         self.ekx = self.ekz = self.kx = self.kz = None
         self.nxz = (0, 0)
+        self.nh = 0
+        self.hist = self.joint = self.quad = None
+        self.h_planes = self.h_names = self.h_centre = self.h_halfwidth = None
+
+    def add_histograms(self, h: dict):
+        """One sample of the per-plane histograms (the dict of ``ChannelFlow.plane_histograms``: planes,
+        names, hist, joint, quad, centre, halfwidth).  The first sample's centre and half-width are
+        frozen (``pdf_frozen``): counts only add on the same bins, so a later sample binned otherwise
+        is refused."""
+        hist, joint = np.asarray(h["hist"], np.uint64), np.asarray(h["joint"], np.uint64)
+        quad = np.asarray(h["quad"], float)
+        centre, halfwidth = np.asarray(h["centre"], float), np.asarray(h["halfwidth"], float)
+        planes, names = [int(j) for j in h["planes"]], [str(s) for s in h["names"]]
+        if hist.shape[:2] != (len(names), len(planes)) or joint.shape[0] != len(planes) or quad.shape != (8, len(planes)):
+            raise ValueError(f"histograms of shape {hist.shape}, {joint.shape}, {quad.shape} for {len(names)} fields, {len(planes)} planes")
+        if self.nh == 0:
+            self.hist, self.joint, self.quad = np.zeros_like(hist), np.zeros_like(joint), np.zeros_like(quad)
+            self.h_planes, self.h_names = planes, names
+            self.h_centre, self.h_halfwidth = centre.copy(), halfwidth.copy()
+        elif (planes != self.h_planes or names != self.h_names or hist.shape != self.hist.shape
+              or joint.shape != self.joint.shape):
+            raise ValueError("histograms of other planes, fields or bin counts than the first sample's")
+        elif not (np.array_equal(centre, self.h_centre) and np.array_equal(halfwidth, self.h_halfwidth)):
+            raise ValueError("histograms binned with another centre or halfwidth than the frozen ones of the first sample")
+        self.hist += hist
+        self.joint += joint
+        self.quad += quad
+        self.nh += 1
+
+    def pdf_frozen(self):
+        """(centre, halfwidth) of the first histogram sample, each (nhf, np), or None before it."""
+        return None if self.nh == 0 else (self.h_centre, self.h_halfwidth)
+
+    def pdfs(self) -> dict:
+        """Summed histograms folded onto the lower half.  Two-dimensional, so kept out of ``profiles``:
+
+          planes, y_plus        [h]       the lower-half plane of every row and its wall distance
+          bin_centres[name]     [nb]      in units of the frozen half-width, from the frozen centre
+          pdf[name]             [h, nb]   density in those units; integrates to 1 - out_of_range[name]
+          out_of_range[name]    [h]       fraction of samples in the under- and overflow bins
+          jpdf_uv               [h, nj, nj]  joint density of (u', v) in the same units (axes u, v)
+          quadrant_fraction     [4, h]    share of samples in Q1 .. Q4
+          quadrant_uv_plus      [4, h]    their contributions to <u'v>+ (the sum over the four is <u'v>+)
+
+        A plane j and its mirror NY - 1 - j are folded when both were sampled, a single one stands
+        alone.  The upper half is reflected (y -> -y): the bins of v, omega_x, omega_z and the v axis of
+        the joint histogram are reversed, which is exact because the bins are symmetric about the
+        centre, Q1 <-> Q4 and Q2 <-> Q3 are swapped and u'v changes sign."""
+        if self.nh == 0 or self.n == 0:
+            raise ValueError("no histogram samples")
+        from ..reference.pdfs import ODD_FIELDS
+
+        n = self.y.size
+        ut, nu = self.utau(), self.nu
+        pos = {j: i for i, j in enumerate(self.h_planes)}
+        rows = sorted({min(j, n - 1 - j) for j in self.h_planes})
+        nb, nj = self.hist.shape[2] - 2, self.joint.shape[1] - 2
+        hist = np.zeros((len(self.h_names), len(rows), nb + 2))
+        joint = np.zeros((len(rows), nj + 2, nj + 2))
+        quad = np.zeros((8, len(rows)))
+        swap = [3, 2, 1, 0]
+        for r, j in enumerate(rows):
+            parts = 0
+            if j in pos:
+                i = pos[j]
+                hist[:, r] += self.hist[:, i]
+                joint[r] += self.joint[i]
+                quad[:, r] += self.quad[:, i]
+                parts += 1
+            if n - 1 - j != j and n - 1 - j in pos:
+                i = pos[n - 1 - j]
+                for f, name in enumerate(self.h_names):
+                    hist[f, r] += self.hist[f, i][::-1] if name in ODD_FIELDS else self.hist[f, i]
+                joint[r] += self.joint[i][:, ::-1]
+                quad[:4, r] -= self.quad[swap, i]
+                quad[4:, r] += self.quad[4:][swap, i]
+                parts += 1
+            quad[:, r] /= parts * self.nh
+        out = {"planes": np.array(rows), "y_plus": (1.0 + self.y[rows]) * ut / nu, "pdf": {}, "bin_centres": {},
+               "out_of_range": {}}
+        for f, name in enumerate(self.h_names):
+            tot = hist[f].sum(-1, keepdims=True)
+            out["pdf"][name] = hist[f][:, 1:-1] / tot / (2.0 / nb)
+            out["out_of_range"][name] = (hist[f][:, 0] + hist[f][:, -1]) / tot[:, 0]
+            out["bin_centres"][name] = (np.arange(nb) + 0.5) * (2.0 / nb) - 1.0
+        out["jpdf_uv"] = joint[:, 1:-1, 1:-1] / joint.sum((1, 2))[:, None, None] / (2.0 / nj) ** 2
+        out["quadrant_fraction"] = quad[4:]
+        out["quadrant_uv_plus"] = quad[:4] / ut ** 2
+        return out
 
     def add_spectra(self, ekx, ekz, kx, kz, nx: int | None = None, nz: int | None = None):
         """One sample of the 1-D spectra at every plane (``Solver.plane_spectra``): ``ekx`` [8, NY, nkx]

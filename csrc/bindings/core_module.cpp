@@ -100,7 +100,8 @@ PYBIND11_MODULE(_core, m) {
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
       RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every)
-      RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure);
+      RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure)
+      RW(pdf_every) RW(pdf_planes) RW(pdf_bins) RW(pdf_joint_bins) RW(pdf_span) RW(pdf_vorticity);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -297,6 +298,43 @@ PYBIND11_MODULE(_core, m) {
       .def("plane_moments",
            [](Solver& s) { return profile_rows(s, &Solver::plane_moments, kMomRows); },
            "plane means of u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4: (11, NY) (one rank)")
+      .def("plane_histograms",
+           [](Solver& s, const std::vector<int>& planes, int nbins, int njoint, double span, bool vorticity,
+              const std::vector<double>& centre, const std::vector<double>& halfwidth) {
+             Solver::PlaneHistograms ph;
+             {
+               py::gil_scoped_release r;
+               ph = s.plane_histograms(planes, nbins, njoint, span, vorticity, centre, halfwidth);
+             }
+             const py::ssize_t np = static_cast<py::ssize_t>(ph.planes.size()), nhf = static_cast<py::ssize_t>(ph.names.size());
+             auto counts = [](const std::vector<unsigned long long>& v, std::vector<py::ssize_t> shape) {
+               py::array_t<std::uint64_t> a(shape);
+               std::copy(v.begin(), v.end(), a.mutable_data());
+               return a;
+             };
+             auto reals = [](const std::vector<double>& v, std::vector<py::ssize_t> shape) {
+               py::array_t<double> a(shape);
+               std::copy(v.begin(), v.end(), a.mutable_data());
+               return a;
+             };
+             py::dict d;
+             d["planes"] = ph.planes;
+             d["names"] = ph.names;
+             d["nbins"] = ph.nb;
+             d["njoint"] = ph.nj;
+             d["hist"] = counts(ph.hist, {nhf, np, ph.nb + 2});
+             d["joint"] = counts(ph.joint, {np, ph.nj + 2, ph.nj + 2});
+             d["quad"] = reals(ph.quad, {static_cast<py::ssize_t>(kQuadRows), np});
+             d["centre"] = reals(ph.centre, {nhf, np});
+             d["halfwidth"] = reals(ph.halfwidth, {nhf, np});
+             return d;
+           },
+           py::arg("planes"), py::arg("nbins") = 128, py::arg("njoint") = 64, py::arg("span") = 8.0, py::arg("vorticity") = false,
+           py::arg("centre") = std::vector<double>(), py::arg("halfwidth") = std::vector<double>(),
+           "histograms of u, v, w (vorticity: and wx, wy, wz) at the given planes: hist (nhf, np, nbins + 2) and joint (u, v) "
+           "(np, njoint + 2, njoint + 2) uint64 with under- and overflow bins, quad (8, np): plane means of u'v over Q1..Q4 "
+           "and the quadrants' sample fractions, and the centre and halfwidth used, (nhf, np); centre / halfwidth are "
+           "flattened (nhf, np) arrays or empty (one rank)")
       .def("gradient_sums",
            [](Solver& s) { return profile_rows(s, &Solver::gradient_sums, kGradRows); },
            "velocity-gradient plane sums wxwx, wywy, wzwz, guu, gvv, gww, guv of the current state: (7, NY), "

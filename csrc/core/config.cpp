@@ -231,6 +231,12 @@ Config Config::from_tree(const ConfigTree& t) {
   c.pstrain_every = static_cast<int>(t.get_int(pick(t, "pstrain_every"), c.pstrain_every));
   c.yspectra_every = static_cast<int>(t.get_int(pick(t, "yspectra_every"), c.yspectra_every));
   c.yspectra_pressure = static_cast<int>(t.get_int(pick(t, "yspectra_pressure"), c.yspectra_pressure));
+  c.pdf_every = static_cast<int>(t.get_int(pick(t, "pdf_every"), c.pdf_every));
+  c.pdf_planes = t.get_string(pick(t, "pdf_planes"), c.pdf_planes);
+  c.pdf_bins = static_cast<int>(t.get_int(pick(t, "pdf_bins"), c.pdf_bins));
+  c.pdf_joint_bins = static_cast<int>(t.get_int(pick(t, "pdf_joint_bins"), c.pdf_joint_bins));
+  c.pdf_span = t.get_double(pick(t, "pdf_span"), c.pdf_span);
+  c.pdf_vorticity = static_cast<int>(t.get_int(pick(t, "pdf_vorticity"), c.pdf_vorticity));
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -288,6 +294,13 @@ std::vector<int> Config::fields_plane_list() const {
 
 std::vector<std::string> Config::fields_list() const { return split_list(fields); }
 
+std::vector<int> Config::pdf_plane_list() const {
+  std::vector<int> out = int_list(pdf_planes, "pdf_planes");
+  if (out.empty())
+    for (int j = 0; j < NY; ++j) out.push_back(j);
+  return out;
+}
+
 int phys_field_index(const std::string& name) {
   static const char* kNames[6] = {"u", "v", "w", "wx", "wy", "wz"};
   for (int f = 0; f < 6; ++f)
@@ -328,7 +341,7 @@ void Config::validate() const {
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
                spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
-               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0 && yspectra_every >= 0,
+               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0 && yspectra_every >= 0 && pdf_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(yspectra_pressure == 0 || yspectra_pressure == 1, "yspectra_pressure must be 0|1");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
@@ -341,6 +354,13 @@ void Config::validate() const {
   CH_CHECK(!fields_list().empty(), "fields must name at least one of u, v, w, wx, wy, wz, p");
   for (const std::string& f : fields_list())
     CH_CHECK(phys_field_index(f) >= 0, "fields: unknown field '" << f << "' (u, v, w, wx, wy, wz, p)");
+  for (int j : pdf_plane_list())
+    CH_CHECK(j >= 0 && j < NY, "pdf_planes: y index " << j << " outside [0, NY)");
+  CH_CHECK(pdf_bins >= 2 && pdf_bins % 2 == 0 && pdf_bins <= 256, "pdf_bins must be even, in [2, 256]");
+  CH_CHECK(pdf_joint_bins >= 1 && pdf_joint_bins <= 64 && pdf_bins % pdf_joint_bins == 0,
+           "pdf_joint_bins must divide pdf_bins and be at most 64");
+  CH_CHECK(pdf_span > 0, "pdf_span must be positive");
+  CH_CHECK(pdf_vorticity == 0 || pdf_vorticity == 1, "pdf_vorticity must be 0|1");
 }
 
 std::string Config::to_string() const {
@@ -373,6 +393,9 @@ std::string Config::to_string() const {
   o << "  pressure_every = " << pressure_every << ";\n";
   o << "  pstrain_every = " << pstrain_every << ";\n";
   o << "  yspectra_every = " << yspectra_every << ";\n  yspectra_pressure = " << yspectra_pressure << ";\n";
+  o << "  pdf_every = " << pdf_every << ";\n  pdf_planes = \"" << pdf_planes << "\";\n";
+  o << "  pdf_bins = " << pdf_bins << ";\n  pdf_joint_bins = " << pdf_joint_bins << ";\n";
+  o << "  pdf_span = " << pdf_span << ";\n  pdf_vorticity = " << pdf_vorticity << ";\n";
   o << "};\n";
   return o.str();
 }

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <functional>
 #include <string>
@@ -287,7 +288,7 @@ void Solver::write_spectra_files(const Spectra& sp) {
 // plane tiles of the wide kernels), so a run of planes is transformed as it is requested.
 void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
                            const std::function<void(int, int, const void*)>& sink, double* d_triple, bool pres,
-                           double* d_pmom) {
+                           double* d_pmom, const ZRealArgs* hist) {
   CH_CHECK(!comm_, "physical-space export is single-rank: it needs a solver without a communicator");
   const Plan& p = plan_;
   if (!prepared_) prepare();
@@ -333,6 +334,17 @@ void Solver::export_planes(const std::vector<int>& ys, int nf, unsigned out_mask
     za.triple = d_triple;
     za.pres = pres ? 1 : 0;
     za.pmom = d_pmom;
+    if (hist) {  // (the tables and outputs of the histogram pass)
+      za.nhf = hist->nhf;
+      za.nb = hist->nb;
+      za.nj = hist->nj;
+      za.hcentre = hist->hcentre;
+      za.hscale = hist->hscale;
+      za.hist = hist->hist;
+      za.joint = hist->joint;
+      za.quad = hist->quad;
+      za.hmerge = hist->hmerge;
+    }
     zreal(za, phys_, tw_z_, fp64_, s_comp_);
     if (nslots) {
       host.resize(static_cast<size_t>(nslots) * ny * plane * tsz);
@@ -413,6 +425,194 @@ std::vector<double> Solver::transport_moments() {
   std::vector<double> m(nt);
   reduce_fetch(d_mom_ + n, nt, m.data());
   return m;
+}
+
+// ---- histograms ------------------------------------------------------------------------------------
+namespace {
+// the compact first derivative of a profile on the host (grid.hpp: tridiag(lo, 1, up) f' = rhs)
+std::vector<double> d1_profile(const YGrid& g, const std::vector<double>& f) {
+  const int N = g.N;
+  std::vector<double> r(N), c(N), d(N);
+  for (int j = 1; j < N - 1; ++j) r[j] = g.d1_rm[j] * f[j - 1] + g.d1_rc[j] * f[j] + g.d1_rp[j] * f[j + 1];
+  r[0] = g.d1_w0[0] * f[0] + g.d1_w0[1] * f[1] + g.d1_w0[2] * f[2];
+  r[N - 1] = g.d1_wN[0] * f[N - 1] + g.d1_wN[1] * f[N - 2] + g.d1_wN[2] * f[N - 3];
+  c[0] = g.d1_up[0];
+  d[0] = r[0];
+  for (int j = 1; j < N; ++j) {
+    const double m = 1.0 - g.d1_lo[j] * c[j - 1];
+    c[j] = g.d1_up[j] / m;
+    d[j] = (r[j] - g.d1_lo[j] * d[j - 1]) / m;
+  }
+  for (int j = N - 2; j >= 0; --j) d[j] -= c[j] * d[j + 1];
+  return d;
+}
+const char* const kHistNames[6] = {"u", "v", "w", "wx", "wy", "wz"};
+}  // namespace
+
+// CHANNEL_HIST_MERGE=0|1: one LDS atomic per sample, or equal consecutive bins of a thread's 16-byte
+// piece merged into one (A/B; profiles/pdfs/README.md has the measurement behind the default)
+static int hist_merge_env() {
+  const char* e = std::getenv("CHANNEL_HIST_MERGE");
+  return e ? (std::atoi(e) != 0 ? 1 : 0) : 1;
+}
+
+Solver::PlaneHistograms Solver::plane_histograms(const std::vector<int>& planes, int nbins, int njoint, double span,
+                                                 bool vorticity, const std::vector<double>& centre,
+                                                 const std::vector<double>& halfwidth) {
+  CH_CHECK(!comm_, "plane_histograms: the export is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const int N = p.NY, nhf = vorticity ? 6 : 3, np = static_cast<int>(planes.size());
+  CH_CHECK(np > 0, "plane_histograms: no planes requested");
+  for (int y : planes) CH_CHECK(y >= 0 && y < N, "plane_histograms: plane " << y << " outside [0, NY)");
+  CH_CHECK(distinct_sorted(planes).size() == planes.size(), "plane_histograms: a plane is listed twice");
+  CH_CHECK(nbins >= 2 && nbins % 2 == 0 && nbins <= kHistMaxBins, "plane_histograms: nbins must be even, in [2, " << kHistMaxBins << "]");
+  CH_CHECK(njoint >= 1 && njoint <= kHistMaxJoint && nbins % njoint == 0,
+           "plane_histograms: njoint must divide nbins and be at most " << kHistMaxJoint);
+  CH_CHECK(span > 0, "plane_histograms: span must be positive");
+  const size_t nfp = static_cast<size_t>(nhf) * np;
+  CH_CHECK(centre.empty() || centre.size() == nfp, "plane_histograms: centre must have shape (" << nhf << ", " << np << ")");
+  CH_CHECK(halfwidth.empty() || halfwidth.size() == nfp, "plane_histograms: halfwidth must have shape (" << nhf << ", " << np << ")");
+  for (double h : halfwidth) CH_CHECK(h > 0 && std::isfinite(h), "plane_histograms: halfwidth must be positive");
+  for (double c : centre) CH_CHECK(std::isfinite(c), "plane_histograms: centre must be finite");
+  if (!prepared_) prepare();
+
+  PlaneHistograms out;
+  out.planes = planes;
+  out.names.assign(kHistNames, kHistNames + nhf);
+  out.nb = nbins;
+  out.nj = njoint;
+  out.centre = centre;
+  out.halfwidth = halfwidth;
+  if (centre.empty()) {
+    out.centre.assign(nfp, 0.0);
+    const std::vector<double> U = mean_profile();
+    const std::vector<double> dU = vorticity ? d1_profile(grid_, U) : std::vector<double>();
+    for (int i = 0; i < np; ++i) {
+      out.centre[i] = U[planes[i]];
+      if (vorticity) out.centre[5 * static_cast<size_t>(np) + i] = -dU[planes[i]];
+    }
+  }
+  if (halfwidth.empty()) {
+    // the r.m.s. of the state that is binned: <u'^2>, <v^2>, <w^2> are rows 1..3 of the moments
+    out.halfwidth.assign(nfp, 1.0);
+    const std::vector<double> m = plane_moments();
+    const std::vector<double> g = vorticity ? gradient_sums() : std::vector<double>();
+    for (int f = 0; f < nhf; ++f)
+      for (int i = 0; i < np; ++i) {
+        const double ms = f < 3 ? m[static_cast<size_t>(1 + f) * N + planes[i]] : g[static_cast<size_t>(f - 3) * N + planes[i]];
+        // the r.m.s. rounded to 12 significant bits: the plane sums are atomic and differ in their last
+        // bits from call to call, which must not move the bin edges between two calls on one state
+        int ex = 0;
+        const double mant = ms > 0 && std::isfinite(ms) ? std::frexp(std::sqrt(ms), &ex) : 0.0;
+        const double rms = std::ldexp(std::round(mant * 4096.0) / 4096.0, ex);
+        if (rms > 0) out.halfwidth[static_cast<size_t>(f) * np + i] = span * rms;
+      }
+  }
+
+  // device: hist [nhf][NY][nb + 2] and joint [NY][nj + 2][nj + 2] (64-bit counts), quad [kQuadRows][NY],
+  // then centre and scale [nhf][NY] (planes that are not requested: 0 and 1, never read)
+  const size_t hb2 = nbins + 2, jb2 = njoint + 2;
+  const size_t nh = static_cast<size_t>(nhf) * N * hb2, nj2 = static_cast<size_t>(N) * jb2 * jb2, nq = static_cast<size_t>(kQuadRows) * N;
+  const size_t ncs = static_cast<size_t>(nhf) * N;
+  const size_t need = (nh + nj2 + nq + 2 * ncs) * 8;
+  if (hist_n_ < need) {
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    if (d_hist_) HIP_CHECK(hipFree(d_hist_));
+    if (h_hist_) HIP_CHECK(hipHostFree(h_hist_));
+    d_hist_ = h_hist_ = nullptr;
+    hist_n_ = 0;
+    HIP_CHECK(hipMalloc(&d_hist_, need));
+    // (through pinned memory: a copy into fresh pageable vectors runs at a fraction of the link's rate)
+    HIP_CHECK(hipHostMalloc(&h_hist_, need, hipHostMallocDefault));
+    hist_n_ = need;
+  }
+  unsigned long long* d_h = static_cast<unsigned long long*>(d_hist_);
+  double* d_q = reinterpret_cast<double*>(d_h + nh + nj2);
+  std::vector<double> cs(2 * ncs, 0.0);
+  std::fill(cs.begin() + ncs, cs.end(), 1.0);
+  for (int f = 0; f < nhf; ++f)
+    for (int i = 0; i < np; ++i) {
+      cs[static_cast<size_t>(f) * N + planes[i]] = out.centre[static_cast<size_t>(f) * np + i];
+      cs[ncs + static_cast<size_t>(f) * N + planes[i]] = nbins / (2.0 * out.halfwidth[static_cast<size_t>(f) * np + i]);
+    }
+  HIP_CHECK(hipMemsetAsync(d_hist_, 0, (nh + nj2 + nq) * 8, s_comp_));
+  HIP_CHECK(hipMemcpyAsync(d_q + nq, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, s_comp_));
+  ZRealArgs hz;
+  hz.nhf = nhf;
+  hz.nb = nbins;
+  hz.nj = njoint;
+  hz.hcentre = d_q + nq;
+  hz.hscale = d_q + nq + ncs;
+  hz.hist = d_h;
+  hz.joint = d_h + nh;
+  hz.quad = d_q;
+  hz.hmerge = hist_merge_env();
+  export_planes(distinct_sorted(planes), nhf, 0u, nullptr, nullptr, nullptr, false, nullptr, &hz);
+  const unsigned long long* h = static_cast<const unsigned long long*>(h_hist_);
+  HIP_CHECK(hipMemcpyAsync(h_hist_, d_hist_, (nh + nj2 + nq) * 8, hipMemcpyDeviceToHost, s_comp_));
+  wait(s_comp_);
+  out.hist.resize(nfp * hb2);
+  out.joint.resize(static_cast<size_t>(np) * jb2 * jb2);
+  out.quad.resize(static_cast<size_t>(kQuadRows) * np);
+  const double* hq = reinterpret_cast<const double*>(h + nh + nj2);
+  const double inv = 1.0 / (static_cast<double>(p.NX) * p.Nzp);
+  for (int i = 0; i < np; ++i) {
+    const size_t y = static_cast<size_t>(planes[i]);
+    for (int f = 0; f < nhf; ++f)
+      std::copy(h + (f * static_cast<size_t>(N) + y) * hb2, h + (f * static_cast<size_t>(N) + y + 1) * hb2,
+                out.hist.begin() + (static_cast<size_t>(f) * np + i) * hb2);
+    std::copy(h + nh + y * jb2 * jb2, h + nh + (y + 1) * jb2 * jb2, out.joint.begin() + static_cast<size_t>(i) * jb2 * jb2);
+    for (int q = 0; q < kQuadRows; ++q) out.quad[static_cast<size_t>(q) * np + i] = hq[static_cast<size_t>(q) * N + y] * inv;
+  }
+  return out;
+}
+
+// <path>PDF_<step>.npy (nhf, np, nb + 2), <path>JPDF_UV_<step>.npy (np, nj + 2, nj + 2), both uint64,
+// <path>QUAD_<step>.npy (8, np) float64 and a sidecar <path>PDF_<step>.json with the centres and
+// half-widths of this write (each write bins about its own step's r.m.s.)
+void Solver::write_pdf_files() {
+  if (comm_) return note_once(pdf_note_, plan_.rank,
+                              "[channel] pdf_every: PDF_*.npy, JPDF_UV_*.npy, QUAD_*.npy skipped (the export is single-rank)\n");
+  const std::vector<int> planes = distinct_sorted(cfg_.pdf_plane_list());
+  const PlaneHistograms ph = plane_histograms(planes, cfg_.pdf_bins, cfg_.pdf_joint_bins, cfg_.pdf_span, cfg_.pdf_vorticity != 0);
+  const size_t nhf = ph.names.size(), np = planes.size();
+  char step[16];
+  std::snprintf(step, sizeof(step), "%08ld", nstep_);
+  auto put = [&](const char* name, const char* descr, const std::string& shape, const void* v, size_t bytes) {
+    const std::string fn = cfg_.path + name + step + ".npy";
+    std::ofstream f(fn, std::ios::binary | std::ios::trunc);
+    CH_CHECK(f.good(), "cannot open '" << fn << "'");
+    const std::string h = npy_header(descr, shape);
+    f.write(h.data(), static_cast<std::streamsize>(h.size()));
+    f.write(static_cast<const char*>(v), static_cast<std::streamsize>(bytes));
+    f.close();
+    CH_CHECK(!f.fail(), "writing '" << fn << "' failed");
+  };
+  auto s = [](size_t v) { return std::to_string(v); };
+  put("PDF_", "<u8", "(" + s(nhf) + ", " + s(np) + ", " + s(ph.nb + 2) + ")", ph.hist.data(), ph.hist.size() * 8);
+  put("JPDF_UV_", "<u8", "(" + s(np) + ", " + s(ph.nj + 2) + ", " + s(ph.nj + 2) + ")", ph.joint.data(), ph.joint.size() * 8);
+  put("QUAD_", "<f8", "(" + s(kQuadRows) + ", " + s(np) + ")", ph.quad.data(), ph.quad.size() * 8);
+  std::ofstream js(cfg_.path + "PDF_" + step + ".json");
+  js.precision(17);
+  js << "{\"step\": " << nstep_ << ", \"time\": " << time() << ", \"planes\": [";
+  for (size_t i = 0; i < np; ++i) js << (i ? ", " : "") << planes[i];
+  js << "], \"y\": [";
+  for (size_t i = 0; i < np; ++i) js << (i ? ", " : "") << grid_.y[planes[i]];
+  js << "], \"names\": [";
+  for (size_t k = 0; k < nhf; ++k) js << (k ? ", " : "") << "\"" << ph.names[k] << "\"";
+  js << "], \"nbins\": " << ph.nb << ", \"njoint\": " << ph.nj << ", \"span\": " << cfg_.pdf_span << ", \"Re\": " << cfg_.Re;
+  auto rows = [&](const char* key, const std::vector<double>& v) {
+    js << ", \"" << key << "\": [";
+    for (size_t k = 0; k < nhf; ++k) {
+      js << (k ? ", [" : "[");
+      for (size_t i = 0; i < np; ++i) js << (i ? ", " : "") << v[k * np + i];
+      js << "]";
+    }
+    js << "]";
+  };
+  rows("centre", ph.centre);
+  rows("halfwidth", ph.halfwidth);
+  js << "}\n";
 }
 
 // ---- pressure ------------------------------------------------------------------------------------

@@ -95,6 +95,12 @@ struct Config {
   int pstrain_every = 0;               // 0 = off; pressure-strain profiles of the uu, vv, ww, uv budgets (PS_*.dat; one rank)
   int yspectra_every = 0;              // 0 = off; 1-D spectra and co-spectra at every plane (YSPEC_KX_<step>.npy, YSPEC_KZ_<step>.npy, YSPEC_<step>.json; any P)
   int yspectra_pressure = 0;           // 1 = also the pressure row of those spectra (one rank)
+  int pdf_every = 0;                   // 0 = off; histograms, joint (u, v) histogram and quadrant sums (PDF_<step>.npy, JPDF_UV_<step>.npy, QUAD_<step>.npy, PDF_<step>.json; one rank)
+  std::string pdf_planes = "";         // comma-separated y indices ("" = every plane)
+  int pdf_bins = 128;                  // bins per 1-D histogram (even, at most 256)
+  int pdf_joint_bins = 64;             // bins per axis of the joint histogram (divides pdf_bins, at most 64)
+  double pdf_span = 8.0;               // half-width of the binned range in plane r.m.s.
+  int pdf_vorticity = 0;               // 1 = also omega_x, omega_y, omega_z
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});
@@ -106,6 +112,7 @@ struct Config {
   std::vector<int> spectra_plane_list() const;   // parsed spectra_planes (default {NY/2})
   std::vector<int> fields_plane_list() const;    // parsed fields_planes (default: 0 .. NY-1)
   std::vector<std::string> fields_list() const;  // parsed fields
+  std::vector<int> pdf_plane_list() const;       // parsed pdf_planes (default: 0 .. NY-1)
 };
 
 // FFT lengths the transform kernels are instantiated for: 2^k (16..2048) and 3, 5, 7, 9, 11, 13, 15 x 2^k

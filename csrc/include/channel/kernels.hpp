@@ -304,9 +304,27 @@ struct ZRealArgs {
   // are stored as complex [row][kz] at spec_out, x-expanded like the inputs (what xfft_forward reads).
   // spec_out may be the place of field 3: a row's Pi is loaded before its r is stored.
   void* spec_out = nullptr;
+  // histograms (optional, with hist set; an instantiation of its own with one plane per block: grid =
+  // ny * ceil(NX / rows per block); no real output, moments or pressure mode beside it): nhf = nfields =
+  // 3 (u, v, w) or 6 (+ omega_x, omega_y, omega_z) fields, nb bins per 1-D histogram, nj | nb bins per
+  // axis of the joint histogram of (u, v).  A sample x of field f at plane y, widened to double, has
+  // i = floor((x - hcentre[f][y]) * hscale[f][y] + nb / 2) (product and sum rounded separately) and goes
+  // to bin 0 (i < 0 or not a number), nb + 1 (i >= nb) or i + 1; its joint bin per axis is 0, nj + 1 or
+  // i / (nb / nj) + 1.  Counts are accumulated (+=) into hist[nhf][NY][nb + 2] and joint[NY][nj + 2][nj + 2]
+  // (first index: u), and quad[8][NY] receives (+=) the sums of u'v over the quadrants Q1 (u' >= 0,
+  // v >= 0), Q2 (-, +), Q3 (-, -), Q4 (+, -) of u' = u - U(y), then the four sample counts, unscaled.
+  int nhf = 0, nb = 0, nj = 0;
+  const double* hcentre = nullptr;   // device [nhf][NY]
+  const double* hscale = nullptr;    // device [nhf][NY], nb / (2 halfwidth)
+  unsigned long long* hist = nullptr;
+  unsigned long long* joint = nullptr;
+  double* quad = nullptr;
+  int hmerge = 1;                    // equal consecutive bins of a thread's 16-byte piece in one LDS atomic
 };
 constexpr int kTripleRows = 3;  // u'u'v, wwv, u'vv
 constexpr int kPresRows = 5;    // r, r^2, r u', r v, r w
+constexpr int kQuadRows = 8;    // sums of u'v over Q1..Q4, then their sample counts
+constexpr int kHistMaxBins = 256, kHistMaxJoint = 64;  // the block's LDS tables (zreal refuses more)
 void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
 
 // standalone FFT entry points for tests: batched C2C along the contiguous axis

@@ -137,6 +137,25 @@ class Solver {
   // plane means of u'u'v, wwv, u'vv, [kTripleRows][NY] (one rank without a communicator, through the
   // export stage like plane_moments)
   std::vector<double> transport_moments();
+  // Histograms of u, v, w (vorticity: and omega_x, omega_y, omega_z) at the planes `planes` (distinct),
+  // the joint histogram of (u, v) and the quadrant split of u'v (kernels.hpp ZRealArgs::hist has the
+  // binning rule): one rank without a communicator, through the export stage like plane_moments.
+  // centre, halfwidth: [nhf][np] as the planes are listed; empty: centre = U(y) for u, -D1 U for
+  // omega_z and 0 otherwise, halfwidth = span * the plane r.m.s. of the current state about that centre
+  // (plane_moments() for u, v, w, rows 0..2 of gradient_sums() for the vorticity, rounded to 12 significant
+  // bits so that two calls on one state bin alike; 1 where it is 0).
+  struct PlaneHistograms {
+    std::vector<int> planes;
+    std::vector<std::string> names;
+    int nb = 0, nj = 0;
+    std::vector<unsigned long long> hist;   // [nhf][np][nb + 2]: underflow, nb bins, overflow
+    std::vector<unsigned long long> joint;  // [np][nj + 2][nj + 2], (u bin, v bin)
+    std::vector<double> quad;               // [kQuadRows][np]: plane means of u'v over Q1..Q4, then the quadrants' sample fractions
+    std::vector<double> centre, halfwidth;  // [nhf][np], as used
+  };
+  PlaneHistograms plane_histograms(const std::vector<int>& planes, int nbins = 128, int njoint = 64, double span = 8.0,
+                                   bool vorticity = false, const std::vector<double>& centre = {},
+                                   const std::vector<double>& halfwidth = {});
   // Pressure of the current state (one rank without a communicator; kernels.hpp PressureArgs):
   // Pi = p + |u|^2 / 2 per (kx, kz) line in the canonical [y][kx][kz] layout, zero on the mean line.
   // The step's transform stage runs once more into a buffer of its own (d_pres_), so neither the
@@ -241,6 +260,7 @@ class Solver {
   // Pi of the current state into field 0 of d_pres_ (device part of pressure_hat)
   void pressure_device(double* ms = nullptr);
   void write_pstrain_files();
+  void write_pdf_files();
   void write_yspectra_files();
   // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat)
   void static_pressure_device();
@@ -256,7 +276,7 @@ class Solver {
   // in the storage precision), the moments accumulated into d_mom (either may be absent)
   void export_planes(const std::vector<int>& ys, int nf, unsigned out_mask, double* d_mom,
                      const std::function<void(int, int, const void*)>& sink, double* d_triple = nullptr,
-                     bool pres = false, double* d_pmom = nullptr);
+                     bool pres = false, double* d_pmom = nullptr, const ZRealArgs* hist = nullptr);
   // what the diagnostics share (diagnostics.cpp): the arguments of the all-plane spectral reductions
   // for the whole local slab (the fields of the mask `six`, p-hat' on request); fn(byte offset, kx count,
   // global kx start) per kx sub-block; the all-reduce (any communicator) and host copy of n accumulated
@@ -423,6 +443,10 @@ class Solver {
   bool pres_note_ = false;    // the "pressure files skipped" note has been printed
   double* d_pstr_ = nullptr;  // pressure strain: [kPStrainRows][NY]
   bool pstr_note_ = false;    // the "pressure-strain files skipped" note has been printed
+  void* d_hist_ = nullptr;    // histograms: hist, joint (64-bit counts), quad, then centre and scale [nhf][NY]
+  size_t hist_n_ = 0;
+  void* h_hist_ = nullptr;    // pinned host copy of the counts and the quadrant sums
+  bool pdf_note_ = false;     // the "PDF files skipped" note has been printed
   double* d_yspec_ = nullptr;  // plane spectra: ekx [kYSpecRows][NY][Kx+1], then ekz [kYSpecRows][NY][nkz]
   double* h_yspec_ = nullptr;  // pinned host copy of d_yspec_ (the result is 17 MB at the headline grid)
   bool yspec_note_ = false;   // the "pressure row skipped" note has been printed

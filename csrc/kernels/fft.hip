@@ -237,7 +237,16 @@ void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64
            "zreal: the pressure mode takes u, v, w, Pi and U(y), without the triple products");
   CH_CHECK(!a.pmom || a.pres, "zreal: the pressure sums need the pressure mode");
   CH_CHECK(!a.spec_out || a.pres, "zreal: the return trip to spectral space needs the pressure mode");
-  if (a.ny == 0 || (!a.out && !a.moments && !a.pmom && !a.spec_out)) return;
+  if (a.hist) {
+    CH_CHECK(!a.out && !a.moments && !a.pres && !a.triple, "zreal: the histograms take a pass of their own");
+    CH_CHECK((a.nhf == 3 || a.nhf == 6) && a.nfields == a.nhf, "zreal: histograms of 3 (u, v, w) or 6 fields");
+    CH_CHECK(a.nb >= 2 && a.nb % 2 == 0 && a.nj >= 1 && a.nb % a.nj == 0, "zreal: an even number of bins, a multiple of the joint bins");
+    CH_CHECK(a.nb <= kHistMaxBins && a.nj <= kHistMaxJoint,
+             "zreal: the histogram tables of a block hold at most " << kHistMaxBins << " bins and " << kHistMaxJoint << " joint bins per axis");
+    CH_CHECK(a.hcentre && a.hscale && a.joint && a.quad && a.U && a.y0 >= 0 && a.y0 + a.ny <= a.NY,
+             "zreal: the histograms need centres, scales, U(y) and their outputs");
+  }
+  if (a.ny == 0 || (!a.out && !a.moments && !a.pmom && !a.spec_out && !a.hist)) return;
   CH_DISPATCH_N(a.Nzp, fft_zr_len<NN>(a, fields, tw, fp64, s));
   HIP_LAUNCH_CHECK(s);
 }

@@ -2015,14 +2015,42 @@ inline int ztpr_env() {
 // thread writes (r, 0) back into the LDS slots it has just read, the row is forward transformed in
 // place and its retained kz, scaled by 1 / (NX Nzp), go to the x-expanded [row][kz] destination (the
 // forward x transform's input).  Rows past the end transform what the zeros left and store nothing.
+// HIST (ZRealArgs::hist, an instantiation of its own): histograms of the 3 or 6 fields, the joint
+// histogram of (u, v) and the quadrant sums of u'v (kernels.hpp has the binning rule).  A block's rows
+// belong to one plane (grid = planes x ceil(NX / ZWT), rows past the plane's end idle like rows past the
+// end), so it holds one plane's tables: 32-bit counts in LDS, bumped by LDS atomics (equal consecutive
+// bins of a thread's 16-byte piece merged into one, ZRealArgs::hmerge) and added to the 64-bit global
+// counts once per block and non-empty bin.  The quadrant sums take the moments' route.
 template <typename T>
 struct alignas(16) RVec {
   T v[16 / sizeof(T)];
 };
-template <int NZP, typename T, bool PRES = false, bool SPEC = false>
+__device__ __forceinline__ int hist_bin(double x, double c, double sc, int nb) {
+  const double f = floor(__dadd_rn(__dmul_rn(x - c, sc), 0.5 * nb));
+  return !(f >= 0.0) ? 0 : (f >= nb ? nb + 1 : static_cast<int>(f) + 1);
+}
+// joint bin of a 1-D bin: (i / ratio) + 1 inside, mag = ceil(2^20 / ratio) (exact below 2^20 / ratio)
+__device__ __forceinline__ int hist_jbin(int bin, int nb, int nj, unsigned mag) {
+  return bin == 0 ? 0 : (bin > nb ? nj + 1 : static_cast<int>((static_cast<unsigned>(bin - 1) * mag) >> 20) + 1);
+}
+template <int VEC>
+__device__ __forceinline__ void hist_count(unsigned* tab, const int (&idx)[VEC], bool merge) {
+  unsigned c = 1;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    if (j + 1 < VEC && merge && idx[j + 1 < VEC ? j + 1 : j] == idx[j]) {
+      ++c;
+    } else {
+      atomicAdd(tab + idx[j], c);
+      c = 1;
+    }
+  }
+}
+template <int NZP, typename T, bool PRES = false, bool SPEC = false, bool HIST = false>
 __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(T))))
     zreal_kernel(ZRealArgs a, const typename C2<T>::type* fields, const typename C2<T>::type* tw) {
   static_assert(!SPEC || PRES, "the return trip is the pressure mode's");
+  static_assert(!HIST || !PRES, "the histograms take a pass of their own");
   using T2 = typename C2<T>::type;
   constexpr int TPR = zphys_tpr<NZP>(sizeof(T)), ZWT = zphys_rows<NZP, T, TPR>(), NT = ZWT * TPR;
   constexpr int PITCH = FftPitch<NZP>::value;
@@ -2039,25 +2067,39 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
   constexpr int kAccRows = kMomRows + kTripleRows;  // per plane: the moments, then the triple products
   __shared__ double acc[MAXP * kAccRows];
   __shared__ double pacc[PRES ? MAXP * kPresRows : 1];
+  constexpr int kHistTab = 6 * (kHistMaxBins + 2), kJointTab = (kHistMaxJoint + 2) * (kHistMaxJoint + 2);
+  __shared__ unsigned hl[HIST ? kHistTab : 1];   // [field][nb + 2]
+  __shared__ unsigned jl[HIST ? kJointTab : 1];  // [u bin][v bin]
+  __shared__ double qacc[HIST ? kQuadRows : 1];
   const int tid = threadIdx.x, t = tid % TPR, w = tid / TPR;
   for (int i = tid; i < TS; i += NT) tws[i] = tw[i];
   for (int i = tid; i < MAXP * kAccRows; i += NT) acc[i] = 0.0;
   if constexpr (PRES)
     for (int i = tid; i < MAXP * kPresRows; i += NT) pacc[i] = 0.0;
+  if constexpr (HIST) {
+    for (int i = tid; i < kHistTab; i += NT) hl[i] = 0u;
+    for (int i = tid; i < kJointTab; i += NT) jl[i] = 0u;
+    if (tid < kQuadRows) qacc[tid] = 0.0;
+  }
   RVec<T> ku[PRES ? EV : 1], kv[PRES ? EV : 1];  // PRES: u, v of the first pair
   __syncthreads();
   T2* row = s + w * PITCH;
   T2* frow = s + (tid / TPRF) * RWW * PITCH;  // first row of this thread's transform group
   const int ft = tid % TPRF;
   const long long nrows = static_cast<long long>(a.ny) * a.NX;
-  const long long rfirst = static_cast<long long>(blockIdx.x) * ZWT;
+  // HIST: blocks per plane; block b has the rows x = (b % gpp) ZWT + w of plane b / gpp
+  const int gpp = HIST ? (a.NX + ZWT - 1) / ZWT : 1;
+  const int bx = HIST ? static_cast<int>(blockIdx.x % gpp) * ZWT : 0;
+  const long long rfirst = HIST ? static_cast<long long>(blockIdx.x / gpp) * a.NX + bx : static_cast<long long>(blockIdx.x) * ZWT;
   const long long r = rfirst + w;
   // rows past the end run the transforms on zeros (the barriers are block-uniform) and touch no
   // global memory beyond clamped loads
-  const bool rv = r < nrows;
-  const long long rc = rv ? r : nrows - 1;
+  const bool rv = HIST ? bx + w < a.NX : r < nrows;
+  const long long rc = rv ? r : (HIST ? rfirst : nrows - 1);
   const int yl = static_cast<int>(rc / a.NX), pl0 = static_cast<int>(rfirst / a.NX);
-  const double Uy = (PRES || a.moments) ? a.U[a.y0 + yl] : 0.0;
+  const double Uy = (PRES || HIST || a.moments) ? a.U[a.y0 + yl] : 0.0;
+  const int hb2 = HIST ? a.nb + 2 : 1, jb2 = HIST ? a.nj + 2 : 1;
+  const unsigned jmag = HIST ? ((1u << 20) + a.nb / a.nj - 1) / (a.nb / a.nj) : 0u;
   const int npairs = (a.nfields + 1) / 2;
   for (int p = 0; p < npairs; ++p) {
     const bool tv = a.triple && p == 1;  // triple products: w pairs with v (the host checks nfields == 3)
@@ -2091,6 +2133,17 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
     double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double tr[2] = {0, 0};  // (u, v): u'u'v, u'vv; (w, v): wwv
     double pm[kPresRows] = {0, 0, 0, 0, 0};
+    double qs[4] = {0, 0, 0, 0};  // HIST, (u, v): the quadrants' sums of u'v and their counts
+    unsigned qn[4] = {0, 0, 0, 0};
+    double hca = 0, hsa = 0, hcb = 0, hsb = 0;
+    if constexpr (HIST) {
+      hca = a.hcentre[fa * a.NY + a.y0 + yl];
+      hsa = a.hscale[fa * a.NY + a.y0 + yl];
+      if (hb) {
+        hcb = a.hcentre[fb * a.NY + a.y0 + yl];
+        hsb = a.hscale[fb * a.NY + a.y0 + yl];
+      }
+    }
 #pragma unroll
     for (int i = 0; i < EV; ++i) {
       const int nv = t + TPR * i;
@@ -2121,6 +2174,33 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
                 pm[3] += rr * dv;
                 pm[4] += rr * dw;
               }
+            }
+          }
+        }
+        if constexpr (HIST) {
+          if (rv) {
+            int ia[VEC], ib[VEC], ij[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+              ia[j] = hist_bin(static_cast<double>(ra.v[j]), hca, hsa, a.nb);
+              ib[j] = hb ? hist_bin(static_cast<double>(rb.v[j]), hcb, hsb, a.nb) : 0;
+            }
+            hist_count<VEC>(hl + fa * hb2, ia, a.hmerge);
+            if (hb) hist_count<VEC>(hl + fb * hb2, ib, a.hmerge);
+            if (p == 0) {  // (u, v): the joint bin from the 1-D bins, the quadrants of u' = u - U(y)
+#pragma unroll
+              for (int j = 0; j < VEC; ++j) {
+                ij[j] = hist_jbin(ia[j], a.nb, a.nj, jmag) * jb2 + hist_jbin(ib[j], a.nb, a.nj, jmag);
+                const double du = static_cast<double>(ra.v[j]) - Uy, dv = static_cast<double>(rb.v[j]);
+                const int q = du >= 0.0 ? (dv >= 0.0 ? 0 : 3) : (dv >= 0.0 ? 1 : 2);
+                const double uv = du * dv;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                  qs[k] += q == k ? uv : 0.0;
+                  qn[k] += q == k ? 1u : 0u;
+                }
+              }
+              hist_count<VEC>(jl, ij, a.hmerge);
             }
           }
         }
@@ -2183,6 +2263,17 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
         }
       }
     }
+    if constexpr (HIST) {
+      if (p == 0) {
+#pragma unroll
+        for (int q = 0; q < kQuadRows; ++q) {
+          double v = q < 4 ? qs[q % 4] : static_cast<double>(qn[q % 4]);
+#pragma unroll
+          for (int o = (TPR < 64 ? TPR : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+          if (rv && (TPR < 64 ? t == 0 : (tid & 63) == 0)) atomicAdd(&qacc[q], v);
+        }
+      }
+    }
     if constexpr (PRES) {
       if (p == 1 && a.pmom) {  // (block-uniform)
 #pragma unroll
@@ -2223,6 +2314,20 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
       }
     }
   }
+  if constexpr (HIST) {  // the block's plane: one global atomic per non-empty bin
+    __syncthreads();
+    const int y = a.y0 + pl0;
+    for (int i = tid; i < a.nhf * hb2; i += NT) {
+      const unsigned c = hl[i];
+      if (c) atomicAdd(&a.hist[(static_cast<size_t>(i / hb2) * a.NY + y) * hb2 + i % hb2], static_cast<unsigned long long>(c));
+    }
+    for (int i = tid; i < jb2 * jb2; i += NT) {
+      const unsigned c = jl[i];
+      if (c) atomicAdd(&a.joint[static_cast<size_t>(y) * jb2 * jb2 + i], static_cast<unsigned long long>(c));
+    }
+    if (tid < kQuadRows) atomicAdd(&a.quad[tid * a.NY + y], qacc[tid]);
+    return;
+  }
   if (a.moments) {
     __syncthreads();
     const int pl1 = static_cast<int>(min(nrows - 1, rfirst + ZWT - 1) / a.NX);  // last plane of the block's rows
@@ -2244,7 +2349,12 @@ static void zreal_launch(const ZRealArgs& a, const void* fields, const Twiddles&
   const long long nrows = static_cast<long long>(a.ny) * a.NX;
   const long long ngroups = (nrows + ZR - 1) / ZR;
   CH_CHECK(ngroups < (1LL << 31), "zreal: too many rows for one launch");
-  if (a.pres && a.spec_out)
+  if (a.hist) {  // one plane per block
+    const long long nblk = static_cast<long long>(a.ny) * ((a.NX + ZR - 1) / ZR);
+    CH_CHECK(nblk < (1LL << 31), "zreal: too many rows for one launch");
+    hipLaunchKernelGGL((zreal_kernel<NN, T, false, false, true>), dim3(static_cast<unsigned>(nblk)), dim3(ZR * TPR), 0, s, a,
+                       static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
+  } else if (a.pres && a.spec_out)
     hipLaunchKernelGGL((zreal_kernel<NN, T, true, true>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
                        static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
   else if (a.pres)

@@ -1,7 +1,8 @@
-"""Cost of one plane_moments(), one gradient_sums(), one transport_moments(), one pressure solve (the
+"""Cost of one plane_moments(), one plane_histograms() without and with the vorticity, one gradient_sums(), one transport_moments(), one pressure solve (the
 device part of pressure_hat()), one pressure_moments(), one pressure_strain(), one plane_spectra() without and with
 the pressure row and one three-field all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
---skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out."""
+--skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out; --pdfs-only stops after the
+histograms."""
 import json
 import os
 import sys
@@ -30,6 +31,36 @@ for rep in range(2):
     t0 = time.perf_counter()
     m = s.plane_moments()
     res[f"plane_moments_ms_{rep}"] = (time.perf_counter() - t0) * 1e3
+# plane_histograms over every plane, without and with the vorticity: the whole call with the default
+# centres and half-widths (one plane_moments() pass more for the r.m.s.; with the vorticity also one
+# gradient_sums()), and the histogram pass alone with given ones, as every sample after the first of
+# sample_statistics(pdfs=True) runs it; host time of the whole call (memset, launches, the 16 MB copy of the
+# counts and their gathering included).  CHANNEL_HIST_MERGE=0: one LDS atomic per sample (A/B).
+planes = list(range(cfg.NY))
+for name, vort in (("plane_histograms", False), ("plane_histograms_vorticity", True)):
+    ts = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        h = s.plane_histograms(planes, vorticity=vort)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res[name + "_default_ms"] = ts
+    c, hw = [float(v) for v in h["centre"].ravel()], [float(v) for v in h["halfwidth"].ravel()]
+    for merge in ("1", "0"):
+        os.environ["CHANNEL_HIST_MERGE"] = merge
+        ts = []
+        for rep in range(5):
+            t0 = time.perf_counter()
+            h = s.plane_histograms(planes, vorticity=vort, centre=c, halfwidth=hw)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        res[name + ("_ms" if merge == "1" else "_nomerge_ms")] = ts
+    del os.environ["CHANNEL_HIST_MERGE"]
+    res[name + "_over_step"] = min(res[name + "_ms"]) / step_ms
+    res[name + "_over_plane_moments"] = min(res[name + "_ms"]) / res["plane_moments_ms_1"]
+    res[name + "_out_of_range"] = float((h["hist"][:, :, 0] + h["hist"][:, :, -1]).sum() / h["hist"].sum())
+res["plane_histograms_6_over_3"] = min(res["plane_histograms_vorticity_ms"]) / min(res["plane_histograms_ms"])
+if "--pdfs-only" in sys.argv:
+    print(json.dumps(res))
+    sys.exit(0)
 # gradient_sums: the six spectral fields read once (planes y < NY of the padded kz line stride),
 # host time of the whole call (launches, the 21 KB result copy and its synchronisation included)
 nkx, nkz = 2 * (cfg.NX // 3) + 1, (2 * cfg.NZ - 2) // 3 + 1
