@@ -169,8 +169,10 @@ torch::Tensor xfft_f(torch::Tensor phys, int Kx) {
 // headline grid runs -- plane tiles (fp32 NX = 512 / 1024), 16-byte accesses (even nkz),
 // non-temporal spectral accesses (nt) -- on planes y0 .. y0 + ny - 1 of F fields of `rows` planes.
 // specb: 1-D complex buffer of F * spec_rows(rows) * nkx * nkzs elements (nkzs = nkz rounded up to 8)
+// xpitch > 0: the x-expanded rows at that pitch (XArgs::xpitch), phys [F, ny, NX, xpitch] with the
+// columns kz >= nkz left as allocated (zeros)
 torch::Tensor xfft_b_blocked(torch::Tensor specb, int F, int rows, int y0, int ny, int NX, int Kx, int nkz, int nt,
-                             int zero_mean_field, int combine, double ax, double az) {
+                             int zero_mean_field, int combine, double ax, double az, int xpitch) {
   check_dev_tensor(specb, "specb");
   const bool f64 = is_fp64_complex(specb);
   const int nkx = 2 * Kx + 1, nkzs = (nkz + kSpecKzBlock - 1) / kSpecKzBlock * kSpecKzBlock;
@@ -178,11 +180,14 @@ torch::Tensor xfft_b_blocked(torch::Tensor specb, int F, int rows, int y0, int n
   TORCH_CHECK(specb.dim() == 1 && specb.numel() == F * fstride, "specb must hold F blocked fields");
   TORCH_CHECK(y0 >= 0 && ny > 0 && y0 + ny <= rows, "plane range outside the fields");
   TORCH_CHECK(!combine || F == 5, "combine mode: five input fields");
-  auto phys = torch::zeros({combine ? 6 : F, ny, NX, nkz}, specb.options());
+  TORCH_CHECK(xpitch == 0 || xpitch >= nkz, "xpitch below nkz");
+  const int rowp = xpitch ? xpitch : nkz;
+  auto phys = torch::zeros({combine ? 6 : F, ny, NX, rowp}, specb.options());
   XArgs a;
   a.NX = NX; a.nkx = nkx; a.Kx = Kx; a.nkz = nkz; a.ny = ny; a.nfields = F;
+  a.xpitch = xpitch;
   a.field_stride_spec = fstride;
-  a.field_stride_phys = static_cast<long long>(ny) * NX * nkz;
+  a.field_stride_phys = static_cast<long long>(ny) * NX * rowp;
   a.kzb = kSpecKzBlock; a.nkzs = nkzs; a.spec_y0 = y0; a.nt = nt;
   a.zero_mean_field = zero_mean_field;
   XSrc s;
@@ -196,20 +201,24 @@ torch::Tensor xfft_b_blocked(torch::Tensor specb, int F, int rows, int y0, int n
 }
 
 // forward counterpart: phys [F, ny, NX, nkz] -> planes y0 .. y0 + ny - 1 of specb (updated in place)
-torch::Tensor xfft_f_blocked(torch::Tensor phys, torch::Tensor specb, int rows, int y0, int Kx, int nt) {
+// nkz_in > 0: phys is [F, ny, NX, xpitch] with nkz_in retained kz per row (XArgs::xpitch)
+torch::Tensor xfft_f_blocked(torch::Tensor phys, torch::Tensor specb, int rows, int y0, int Kx, int nt, int nkz_in) {
   check_dev_tensor(phys, "phys");
   check_dev_tensor(specb, "specb");
   const bool f64 = is_fp64_complex(phys);
   TORCH_CHECK(phys.dim() == 4, "phys must be [F, ny, NX, nkz]");
-  const int F = phys.size(0), ny = phys.size(1), NX = phys.size(2), nkz = phys.size(3);
+  const int F = phys.size(0), ny = phys.size(1), NX = phys.size(2), rowp = phys.size(3);
+  TORCH_CHECK(nkz_in >= 0 && nkz_in <= rowp, "nkz above the row pitch");
+  const int nkz = nkz_in ? nkz_in : rowp;
   const int nkx = 2 * Kx + 1, nkzs = (nkz + kSpecKzBlock - 1) / kSpecKzBlock * kSpecKzBlock;
   const long long fstride = static_cast<long long>(spec_rows(kSpecKzBlock, rows)) * nkx * nkzs;
   TORCH_CHECK(specb.dim() == 1 && specb.numel() == F * fstride && is_fp64_complex(specb) == f64, "specb mismatch");
   TORCH_CHECK(y0 >= 0 && y0 + ny <= rows, "plane range outside the fields");
   XArgs a;
   a.NX = NX; a.nkx = nkx; a.Kx = Kx; a.nkz = nkz; a.ny = ny; a.nfields = F;
+  a.xpitch = nkz_in ? rowp : 0;
   a.field_stride_spec = fstride;
-  a.field_stride_phys = static_cast<long long>(ny) * NX * nkz;
+  a.field_stride_phys = static_cast<long long>(ny) * NX * rowp;
   a.kzb = kSpecKzBlock; a.nkzs = nkzs; a.spec_y0 = y0; a.nt = nt;
   XDst d;
   d.base = specb.data_ptr();
@@ -223,13 +232,17 @@ torch::Tensor xfft_f_blocked(torch::Tensor phys, torch::Tensor specb, int rows, 
 // z physical stage (tests): fields [6, ny, NX, nkz] -> H [3, ny, NX, nkz], maxima [4].  The planes
 // are rows y0 .. y0 + ny - 1 of the grid inv_dy describes (a chunk of a slab); maxima, when given,
 // is a float32[4] device tensor the kernel accumulates into (the solver's chunks share one)
+// nkz_in > 0: fields is [6, ny, NX, xpitch] with nkz_in retained kz per row (ZArgs::xpitch); H then
+// keeps that shape and its columns kz >= nkz_in are those of the input
 std::pair<torch::Tensor, torch::Tensor> zphys_op(torch::Tensor fields, int Nzp, torch::Tensor inv_dy, double cx, double cz,
-                                                 int y0, py::object maxima_in) {
+                                                 int y0, py::object maxima_in, int nkz_in) {
   check_dev_tensor(fields, "fields");
   const bool f64 = is_fp64_complex(fields);
   TORCH_CHECK(fields.dim() == 4 && fields.size(0) == 6, "fields must be [6, ny, NX, nkz]");
   auto f = fields.clone();
-  const int ny = f.size(1), NX = f.size(2), nkz = f.size(3);
+  const int ny = f.size(1), NX = f.size(2), rowp = f.size(3);
+  TORCH_CHECK(nkz_in >= 0 && nkz_in <= rowp, "nkz above the row pitch");
+  const int nkz = nkz_in ? nkz_in : rowp;
   TORCH_CHECK(y0 >= 0 && inv_dy.dim() == 1 && inv_dy.numel() >= y0 + ny, "inv_dy must have at least y0 + ny entries");
   torch::Tensor maxima;
   if (maxima_in.is_none()) {
@@ -243,7 +256,8 @@ std::pair<torch::Tensor, torch::Tensor> zphys_op(torch::Tensor fields, int Nzp, 
   auto idy = inv_dy.to(fields.device(), torch::kFloat64).contiguous();
   ZArgs a;
   a.NX = NX; a.Nzp = Nzp; a.nkz = nkz; a.ny = ny; a.y0 = y0;
-  a.field_stride = static_cast<long long>(ny) * NX * nkz;
+  a.xpitch = nkz_in ? rowp : 0;
+  a.field_stride = static_cast<long long>(ny) * NX * rowp;
   a.scale = 1.0 / (static_cast<double>(NX) * Nzp);
   a.inv_dy = idy.data_ptr<double>();
   a.cx = cx; a.cz = cz;
@@ -298,7 +312,10 @@ torch::Tensor phys_tensor(Solver& s) {
   auto opts = torch::TensorOptions()
                   .dtype(s.fp64() ? torch::kComplexDouble : torch::kComplexFloat)
                   .device(torch::kCUDA, c10::hip::current_device());
-  return torch::from_blob(s.phys_ptr(), {6, p.ny_loc, p.NX, p.nkz_loc}, opts);
+  // (rows of pitch xexp_pitch() elements, fields phys_field_elems() apart: a strided view of the data columns)
+  const long long rowp = s.xexp_row_pitch() ? s.xexp_row_pitch() : p.nkz_loc;
+  return torch::from_blob(s.phys_ptr(), {6, p.ny_loc, p.NX, p.nkz_loc},
+                          {static_cast<long long>(s.phys_field_elems()), static_cast<long long>(p.NX) * rowp, rowp, 1}, opts);
 }
 
 }  // namespace
@@ -323,11 +340,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xfft_forward", &xfft_f);
   m.def("xfft_backward_blocked", &xfft_b_blocked, py::arg("specb"), py::arg("F"), py::arg("rows"), py::arg("y0"),
         py::arg("ny"), py::arg("NX"), py::arg("Kx"), py::arg("nkz"), py::arg("nt") = 0, py::arg("zero_mean_field") = -1,
-        py::arg("combine") = 0, py::arg("ax") = 1.0, py::arg("az") = 2.0);
+        py::arg("combine") = 0, py::arg("ax") = 1.0, py::arg("az") = 2.0, py::arg("xpitch") = 0);
   m.def("xfft_forward_blocked", &xfft_f_blocked, py::arg("phys"), py::arg("specb"), py::arg("rows"), py::arg("y0"),
-        py::arg("Kx"), py::arg("nt") = 0);
+        py::arg("Kx"), py::arg("nt") = 0, py::arg("nkz") = 0);
   m.def("zphys", &zphys_op, py::arg("fields"), py::arg("Nzp"), py::arg("inv_dy"), py::arg("cx"), py::arg("cz"),
-        py::arg("y0") = 0, py::arg("maxima") = py::none());
+        py::arg("y0") = 0, py::arg("maxima") = py::none(), py::arg("nkz") = 0);
+  m.def("xexp_pitch", [](int nkz) { return xexp_pitch(nkz); }, "row pitch of the one-rank x-expanded layout for nkz retained kz");
   m.def("dt_update", &dt_update_op, py::arg("maxima"), py::arg("cfl"), py::arg("dt_max"), py::arg("dt_fixed"),
         py::arg("parity"), py::arg("NX"), py::arg("NZ"), py::arg("LX"), py::arg("LZ"), py::arg("Re"), py::arg("NY"),
         py::arg("time0") = 0.0,

@@ -184,6 +184,7 @@ ZRealArgs Solver::zreal_args(int y0, int ny, int nf) const {
   za.NX = plan_.NX;
   za.Nzp = plan_.Nzp;
   za.nkz = plan_.nkz;
+  za.xpitch = xpitch_;
   za.ny = ny;
   za.y0 = y0;
   za.nfields = nf;

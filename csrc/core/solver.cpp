@@ -249,7 +249,15 @@ void Solver::alloc() {
   // read back from it); CHANNEL_XNT=0/1 forces it (read per Solver)
   xnt_ = 6ull * spec_ * esz_ > (256ull << 20) ? 1 : 0;
   if (const char* e = std::getenv("CHANNEL_XNT")) xnt_ = std::atoi(e) != 0 ? 1 : 0;
-  physn_ = p.phys_elems();
+  // one rank: the rows of the x-expanded intermediates start on whole 128-B lines (kernels.hpp
+  // xexp_pitch; profiles/xexp/README.md); the P > 1 segment layouts keep rows of nkz_loc.
+  // CHANNEL_XEXP_LAYOUT=0 | 1: rows of nkz at P = 1 too | the padded rows (A/B, tests; read per Solver)
+  xpitch_ = 0;
+  if (!comm_ && p.P == 1) {
+    const char* e = std::getenv("CHANNEL_XEXP_LAYOUT");
+    if (e ? std::atoi(e) != 0 : kXexpPaddedDefault) xpitch_ = xexp_pitch(p.nkz);
+  }
+  physn_ = p.phys_elems(xpitch_);
   // kx sub-blocks (K-SPEC / exchange overlap): slab with a communicator only; the same count on
   // every rank (a function of Pc and the environment), at most kMaxSeg exchange segments in total
   nkb_ = 1;
@@ -875,6 +883,7 @@ XArgs Solver::x_args() const {
   xa.nkx = p.nkx;
   xa.Kx = p.Kx;
   xa.nkz = p.nkz;
+  xa.xpitch = xpitch_;
   xa.ny = p.ny_loc;
   xa.field_stride_phys = static_cast<long long>(physn_);
   // u, v, w, omega_x, omega_y, omega_z: read (omega_y's source is the omega state, whose mean line
@@ -931,6 +940,7 @@ void Solver::transforms(int n, bool /*stats*/, void* dst_fields) {
   za.NX = p.NX;
   za.Nzp = p.Nzp;
   za.nkz = p.nkz;
+  za.xpitch = xpitch_;
   za.ny = p.ny_loc;
   za.y0 = p.y0;
   za.field_stride = static_cast<long long>(physn_);
@@ -986,7 +996,7 @@ void Solver::transforms(int n, bool /*stats*/, void* dst_fields) {
         const int ny = std::min(ychunk_, p.ny_loc - y0);
         hipStream_t cs = streams[ci % nst];
         const size_t so = kzb_ ? 0 : static_cast<size_t>(y0) * p.nkx * p.nkz * esz_;
-        char* ph = static_cast<char*>(phys_) + static_cast<size_t>(y0) * p.NX * p.nkz * esz_;
+        char* ph = static_cast<char*>(phys_) + static_cast<size_t>(y0) * p.NX * (xpitch_ ? xpitch_ : p.nkz) * esz_;
         XArgs xc;
         XSrc sc;
         x_chunk(xa, src, y0, ny, xc, sc);

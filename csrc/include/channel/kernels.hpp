@@ -203,8 +203,20 @@ struct XDst {             // destination blocks for the forward x-transform (per
   const unsigned* rowtab = nullptr;  // as XSrc::rowtab
 };
 
+// ---- x-expanded layout ---------------------------------------------------------------------------
+// The intermediates between the x and z transforms are [y][x][kz] complex rows of row pitch
+// `xpitch` elements.  xpitch = 0 (or nkz): rows packed at nkz elements (the P > 1 segment paths and
+// every caller that does not set it).  One rank: the pitch is rounded up to kXexpAlign elements
+// (xexp_pitch: whole 128-B lines in fp32), so the 64-B tile pieces of the x kernels never straddle a
+// 64-B boundary and a z row starts on a line; the columns kz >= nkz of a row are padding that is
+// neither read as data nor written (profiles/xexp/README.md).
+constexpr int kXexpAlign = 16;
+constexpr bool kXexpPaddedDefault = true;  // the one-rank solver's layout when CHANNEL_XEXP_LAYOUT is unset
+__host__ __device__ constexpr int xexp_pitch(int nkz) { return (nkz + kXexpAlign - 1) / kXexpAlign * kXexpAlign; }
+
 struct XArgs {
   int NX = 0, nkx = 0, Kx = 0, nkz = 0, ny = 0;   // ny = local y planes, nkz = local kz count
+  int xpitch = 0;                    // x-expanded row pitch (one segment only); 0 = nkz
   int nfields = 1;
   long long field_stride_spec = 0;   // element stride between fields in the spectral buffers
   long long field_stride_phys = 0;   // element stride between fields in the physical buffers
@@ -238,7 +250,7 @@ struct XArgs {
   int combine = 0;
   double ax = 1.0, az = 2.0;
 };
-// backward: spectral (truncated kx) -> [y][x][kz] complex, zero padding kx
+// backward: spectral (truncated kx) -> [y][x][kz] complex (row pitch XArgs::xpitch), zero padding kx
 void xfft_backward(const XArgs& a, const XSrc& src, void* phys, const Twiddles& tw, bool fp64, hipStream_t s);
 // forward: [y][x][kz] -> spectral truncated kx (unnormalised)
 void xfft_forward(const XArgs& a, const void* phys, const XDst& dst, const Twiddles& tw, bool fp64, hipStream_t s);
@@ -249,6 +261,7 @@ std::string xfft_last_backward_variant();
 
 struct ZArgs {
   int NX = 0, Nzp = 0, nkz = 0, ny = 0, y0 = 0;   // NX = local x count (rows = ny * NX)
+  int xpitch = 0;                    // row pitch (one segment of all Nzp/3 + 1 kz only): 0 = nkz, or xexp_pitch(nkz)
   // rows blocked by kz range (pencil B exchange): kz in [kz_start[s], kz_start[s+1]) of row r lives
   // at off[s] + r * nkz_s + kz - kz_start[s].  One segment = plain [row][kz].
   int nseg = 1;
@@ -270,11 +283,12 @@ std::string zphys_last_variant();
 void zphys(const ZArgs& a, void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
 
 // export stage (on request, outside the step): the z complex-to-real transform of an x-expanded
-// chunk [f][row][kz] (row = y_local * NX + x, nkz = Nzp/3 + 1, one segment: what xfft_backward
+// chunk [f][row][kz] (row = y_local * NX + x, nkz = Nzp/3 + 1, row pitch xpitch, one segment: what xfft_backward
 // writes and zphys reads) into real rows, and/or the one-point moments of u, v, w per plane
 constexpr int kMomRows = 11;  // u', u'^2, v'^2, w'^2, u'v', u'^3, v'^3, w'^3, u'^4, v'^4, w'^4
 struct ZRealArgs {
   int NX = 0, Nzp = 0, nkz = 0, ny = 0;   // rows = ny * NX
+  int xpitch = 0;                    // row pitch of the inputs and of spec_out (0 = nkz)
   int y0 = 0;                        // global plane of the chunk's first plane (moments, U)
   int nfields = 0;                   // transformed fields, in pairs (an odd count: the last with zero)
   long long field_stride = 0;        // element stride between the input fields

@@ -66,8 +66,9 @@ struct Plan {
   int rank_of(int row, int col) const { return row * Pc + col; }
   int lines_loc() const { return nkx_loc * nkz_loc; }
   size_t spec_elems() const { return static_cast<size_t>(NY) * lines_loc(); }
-  // x-expanded intermediate [y_loc][x][kz_loc] (pencil: blocked by destination x range)
-  size_t phys_elems() const { return static_cast<size_t>(ny_loc) * NX * nkz_loc; }
+  // x-expanded intermediate [y_loc][x][kz_loc] (pencil: blocked by destination x range); pitch > 0:
+  // rows of that many elements (the one-rank layout, kernels.hpp xexp_pitch)
+  size_t phys_elems(int pitch = 0) const { return static_cast<size_t>(ny_loc) * NX * (pitch > 0 ? pitch : nkz_loc); }
   // z-stage rows [y_loc][x_loc][kz] (pencil only; blocked by source kz range)
   size_t zrow_elems() const { return static_cast<size_t>(ny_loc) * nx_loc * nkz; }
   // automatic pencil grid: the most square Pr x Pc with Pr <= Pc

@@ -205,6 +205,9 @@ class Solver {
   bool combine() const { return combine_; }
   void* in_field(int j) const;
   void* phys_ptr() const { return phys_; }
+  // row pitch of the x-expanded buffer in elements (0: rows of nkz_loc) and the elements per field
+  int xexp_row_pitch() const { return xpitch_; }
+  size_t phys_field_elems() const { return physn_; }
   const YTablesDev& ytables() const { return ytab_; }
   // kx sub-blocks of the local spectral layout (1 = plain [y][kx_local][kz]; see nkb_)
   int kblocks() const { return nkb_; }
@@ -329,6 +332,7 @@ class Solver {
   void build_rowtab();
   void* zbuf_ = nullptr;   // pencil: 6 * ny_loc*nx_loc*nkz (B-exchange blocks, z stage in place)
   size_t spec_ = 0, physn_ = 0, xstride_ = 0, zstride_ = 0;
+  int xpitch_ = 0;         // x-expanded row pitch (one rank: xexp_pitch(nkz); 0: rows of nkz_loc)
   // spectral layout (spec_index): kzb_ = 8 (one rank) blocks the lines by 8 kz, with the kz line
   // stride nkzs_ padded to a multiple of 8; canon_ = NY * nkx_loc * nkz_loc, the element count of
   // the canonical host layout [y][kx_loc][kz_loc] (set_state / get_state / restart files)

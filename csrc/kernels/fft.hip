@@ -34,7 +34,7 @@ std::string zphys_last_variant() {
   auto b = [](bool x) { return x ? "true" : "false"; };
   return std::string("zphys_kernel<") + std::to_string(v.nn) + ", " + (v.f64 ? "double" : "float") + ", " + b(v.seg) + ", " +
          b(v.zh) + ", " + std::to_string(v.tpr) + ", " + std::to_string(v.zr) + ", " + std::to_string(v.wpe) + ", " +
-         std::to_string(v.zf) + ", " + b(v.dma) + ">";
+         std::to_string(v.zf) + ", " + b(v.dma) + (v.xp ? ", true>" : ">");  // (the padded row pitch: one more argument)
 }
 
 void Twiddles::build(int n_, bool fp64_) {
@@ -112,6 +112,9 @@ static XArgs norm_pseg(const XArgs& in) {
     a.poff[0] = 0;
   }
   CH_CHECK(a.npseg <= 8 && a.x_start[0] == 0 && a.x_start[a.npseg] == a.NX, "x transform: bad x segment table");
+  // x-expanded row pitch: one segment only (the x-blocked segments keep rows of nkz); 0 = packed rows
+  CH_CHECK(a.xpitch == 0 || (a.npseg == 1 && a.xpitch >= a.nkz), "x transform: a row pitch needs one x segment and pitch >= nkz");
+  if (a.xpitch == 0) a.xpitch = a.nkz;
   return a;
 }
 
@@ -126,10 +129,10 @@ void xfft_backward(const XArgs& a_in, const XSrc& src, void* phys, const Twiddle
     for (int j = 0; j < kCmbInputs; ++j)
       CH_CHECK(src.fld[j] && (src.self_seg < 0 || src.self_fld[j]), "xfft_backward: combine mode input field " << j << " missing");
   }
-  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.nkz < (1LL << 32), "xfft_backward: per-field plane block exceeds 32-bit offsets");
+  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.xpitch < (1LL << 32), "xfft_backward: per-field plane block exceeds 32-bit offsets");
   // one-source / blocked-layout paths address with 32-bit BYTE offsets (fft_impl.hpp at_byte)
   const long long esz = fp64 ? 16 : 8;
-  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.nkz * esz < (1LL << 32),
+  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.xpitch * esz < (1LL << 32),
            "xfft_backward: a field's x-expanded chunk exceeds 4 GiB (use smaller y chunks)");
   CH_CHECK(!a.kzb || (a.combine ? static_cast<long long>(spec_rows(kSpecKzBlock, a.spec_y0 + a.ny)) * a.nkx * a.nkzs
                                : a.field_stride_spec) * esz < (1LL << 32),
@@ -145,10 +148,10 @@ void xfft_forward(const XArgs& a_in, const void* phys, const XDst& dst, const Tw
   const XArgs a = norm_pseg(a_in);
   CH_CHECK(tw.n == a.NX && tw.fp64 == fp64, "xfft_forward: twiddle table mismatch");
   CH_CHECK(a.Kx == a.NX / 3 && a.nkx == 2 * a.Kx + 1, "xfft_forward: retained kx must be the 2/3 rule's (Kx = NX/3)");
-  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.nkz < (1LL << 32), "xfft_forward: per-field plane block exceeds 32-bit offsets");
+  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.xpitch < (1LL << 32), "xfft_forward: per-field plane block exceeds 32-bit offsets");
   CH_CHECK(static_cast<long long>(a.ny) * a.nkx * a.nkz < (1LL << 32), "xfft_forward: per-field spectral block exceeds 32-bit offsets");
   const long long esz = fp64 ? 16 : 8;
-  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.nkz * esz < (1LL << 32),
+  CH_CHECK(static_cast<long long>(a.ny) * a.NX * a.xpitch * esz < (1LL << 32),
            "xfft_forward: a field's x-expanded chunk exceeds 4 GiB (use smaller y chunks)");
   CH_CHECK(!a.kzb || a.field_stride_spec * esz < (1LL << 32), "xfft_forward: blocked spectral field exceeds 4 GiB");
   CH_CHECK(dst.ndst > 1 || dst.self_seg >= 0 || static_cast<long long>(a.ny) * a.nkx * a.nkz * esz < (1LL << 32),
@@ -196,6 +199,9 @@ void zphys(const ZArgs& a_in, void* fields, const Twiddles& tw, bool fp64, hipSt
   CH_CHECK(a.nseg <= 8 && a.kz_start[0] == 0 && a.kz_start[a.nseg] == a.nkz, "zphys: bad kz segment table");
   CH_CHECK(tw.n == a.Nzp && tw.fp64 == fp64, "zphys: twiddle table mismatch");
   CH_CHECK(a.nkz - 1 < a.Nzp / 2, "zphys: retained kz must be below Nyquist");
+  CH_CHECK(a.xpitch == 0 || a.xpitch == a.nkz || (a.nseg == 1 && a.nkz == a.Nzp / 3 + 1 && a.xpitch == xexp_pitch(a.nkz)),
+           "zphys: the row pitch is nkz or xexp_pitch(nkz) of one segment of all retained kz");
+  if (a.xpitch == a.nkz) a.xpitch = 0;
   if (a.ny == 0) return;
   if (a.Nzp == 1024 && zreg_enabled()) {
     CH_CHECK(tw.reg, "zphys: register-FFT twiddles missing");
@@ -227,6 +233,7 @@ void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64
   CH_CHECK(tw.n == a.Nzp && tw.fp64 == fp64, "zreal: twiddle table mismatch");
   CH_CHECK(a.nkz == a.Nzp / 3 + 1, "zreal: one segment of the 2/3 rule's retained kz (Nzp/3 + 1)");
   CH_CHECK(a.NX >= 16, "zreal: at least 16 rows per plane");
+  CH_CHECK(a.xpitch == 0 || a.xpitch >= a.nkz, "zreal: a row pitch below nkz");
   CH_CHECK(a.nfields >= 1 && a.nfields <= 6, "zreal: 1 to 6 fields");
   CH_CHECK(!a.out || ((a.out_mask >> a.nfields) == 0 && a.out_field_stride >= static_cast<long long>(a.ny) * a.NX * a.Nzp &&
                       a.out_field_stride % (fp64 ? 2 : 4) == 0),

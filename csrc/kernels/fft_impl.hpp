@@ -2,8 +2,9 @@
 //
 //  * xfft_backward: for each local y plane and a chunk of C kz columns, gather the retained kx
 //    modes (directly from the all-to-all receive blocks; zero-padded to NX in LDS), inverse C2C of
-//    length NX, write [y][x][kz].  Replaces the x-part of the reference's 2-D cufftExecC2R and the
-//    transposeYZX2XYZ local transposes + dealias (fft.c:54-78, channel_cuda_mpi.c:95-128).
+//    length NX, write [y][x][kz] (rows of pitch XArgs::xpitch: kernels.hpp, "x-expanded layout").
+//    Replaces the x-part of the reference's 2-D cufftExecC2R and the transposeYZX2XYZ local
+//    transposes + dealias (fft.c:54-78, channel_cuda_mpi.c:95-128).
 //  * zphys: per (y,x) row, the six fields u,v,w,wx,wy,wz are paired into three complex rows
 //    (z = a + i b), zero-padded from the retained kz to 2NZ-2 points, inverse FFT'd, the
 //    rotational nonlinear term H = u x omega is formed in registers (rotorkernel,
@@ -586,7 +587,7 @@ __global__ void __launch_bounds__((XCfg<NX, T, WIDE>::NT), (XCfg<NX, T, WIDE>::M
           const SegPos sp = seg_find(a.x_start, a.poff, a.npseg, x);
           *reinterpret_cast<CV*>(out + sp.off + (static_cast<long long>(yy) * sp.count + (x - sp.start)) * a.nkz + kz) = w;
         } else {
-          at_byte(reinterpret_cast<CV*>(out), (static_cast<unsigned>(yy * NX + x) * static_cast<unsigned>(a.nkz) +
+          at_byte(reinterpret_cast<CV*>(out), (static_cast<unsigned>(yy * NX + x) * static_cast<unsigned>(a.xpitch) +
                                                static_cast<unsigned>(kz)) * static_cast<unsigned>(sizeof(T2))) = w;
         }
       }
@@ -667,7 +668,7 @@ __global__ void __launch_bounds__((XCfg<NX, T, WIDE>::NT), (XCfg<NX, T, WIDE>::M
                                             static_cast<unsigned>(yy * sp.count + x - sp.start) * static_cast<unsigned>(a.nkz) +
                                             static_cast<unsigned>(kz));
       } else {
-        v[q] = at_byte(reinterpret_cast<const CV*>(in), (static_cast<unsigned>(yy * NX + x) * static_cast<unsigned>(a.nkz) +
+        v[q] = at_byte(reinterpret_cast<const CV*>(in), (static_cast<unsigned>(yy * NX + x) * static_cast<unsigned>(a.xpitch) +
                                                          static_cast<unsigned>(kz)) * static_cast<unsigned>(sizeof(T2)));
       }
     }
@@ -804,7 +805,7 @@ inline int persist_blocks(const void* kern, int threads, const char* env) {
 // 16-byte accesses (two fp32 complex per lane) need every element offset of a tile row even:
 // nkz even (rows start at multiples of nkz) and every block offset and field stride even
 inline bool xvec_ok(const XArgs& a, const long long* off, int n, long long self_stride, long long self_off) {
-  if (a.nkz % 2 || a.field_stride_spec % 2 || a.field_stride_phys % 2 || self_stride % 2 || self_off % 2) return false;
+  if (a.nkz % 2 || a.xpitch % 2 || a.field_stride_spec % 2 || a.field_stride_phys % 2 || self_stride % 2 || self_off % 2) return false;
   for (int i = 0; i < n; ++i)
     if (off[i] % 2) return false;
   for (int i = 0; i < a.npseg; ++i)
@@ -1045,7 +1046,7 @@ constexpr int zphys_rows() {
 }
 
 template <int NZP, typename T, bool SEG, bool ZH = true, int TPRT = zphys_tpr<NZP>(sizeof(T)),
-          int ZWT = zphys_rows<NZP, T, TPRT>(), int WPE = 2, int ZF = 3, bool DMA = false>
+          int ZWT = zphys_rows<NZP, T, TPRT>(), int WPE = 2, int ZF = 3, bool DMA = false, bool XP = false>
 __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu(WPE), target("no-load-store-opt"))) zphys_kernel(ZArgs a, typename C2<T>::type* fields,
                                                          const typename C2<T>::type* tw) {
   using T2 = typename C2<T>::type;
@@ -1122,6 +1123,10 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
   // one segment holds every retained kz (Nzp/3 + 1: the launcher checks it), a compile-time count,
   // so only the last of a thread's kz slots needs a bound check
   const int nkz = SEG ? a.nkz : NZP / 3 + 1, Kz = nkz - 1;
+  // XP: the rows of the one-segment layout at the padded pitch (kernels.hpp xexp_pitch), a
+  // compile-time constant like nkz; the columns kz >= nkz of a row are never touched
+  static_assert(!XP || !SEG, "zphys: the padded row pitch is the one-segment layout's");
+  constexpr int kRowP = XP ? xexp_pitch(NZP / 3 + 1) : NZP / 3 + 1;
   const long long fs = a.field_stride;
   float mu = 0.f, mv = 0.f, mw = 0.f, mc = 0.f;
   // element offset of (row r, kz) in the kz-blocked row layout (one block: r * nkz + kz, 32-bit:
@@ -1132,7 +1137,7 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
       const SegPos sp = seg_find(a.kz_start, a.off, a.nseg, k);
       return sp.off + r * sp.count + (k - sp.start);
     } else {
-      return static_cast<long long>(static_cast<unsigned>(r) * static_cast<unsigned>(nkz) + static_cast<unsigned>(k));
+      return static_cast<long long>(static_cast<unsigned>(r) * static_cast<unsigned>(kRowP) + static_cast<unsigned>(k));
     }
   };
   // retained kz per thread: nkz = Nzp/3 + 1 (2/3 rule; checked on the host)
@@ -1144,7 +1149,7 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
     if constexpr (!SEG) {
       // unconditional loads at a clamped (in-bounds) index, zeros selected afterwards: a guarded
       // load is a branch, an exec-mask save/restore and a zero move per element
-      const unsigned rb = static_cast<unsigned>(rv ? r : nrows - 1) * static_cast<unsigned>(nkz);
+      const unsigned rb = static_cast<unsigned>(rv ? r : nrows - 1) * static_cast<unsigned>(kRowP);
 #pragma unroll
       for (int i = 0; i < MK; ++i) {
         const int k = t + TPR * i;
@@ -1220,7 +1225,7 @@ __global__ void __launch_bounds__(ZWT * TPRT) __attribute__((amdgpu_waves_per_eu
   auto slot_issue = [&](long long rr, bool live, int ww, int ln) {
     if constexpr (kDma) {
       constexpr int NI = (kSlotPieces + 63) / 64, TAIL = kSlotPieces - 64 * (NI - 1);
-      const unsigned rb = static_cast<unsigned>(rr) * static_cast<unsigned>(kSlotF) * static_cast<unsigned>(sizeof(T2));
+      const unsigned rb = static_cast<unsigned>(rr) * static_cast<unsigned>(kRowP) * static_cast<unsigned>(sizeof(T2));
       const unsigned fsb = static_cast<unsigned>(fs) * static_cast<unsigned>(sizeof(T2));
       T2* const sl = zslot + __builtin_amdgcn_readfirstlane(ww) * kSlotStride;
 #pragma unroll
@@ -1762,7 +1767,7 @@ __global__ void __launch_bounds__(256) zphys_reg_kernel(ZArgs a, typename C2<T>:
       const SegPos sp = seg_find(a.kz_start, a.off, a.nseg, k);
       return sp.off + r * sp.count + (k - sp.start);
     } else {
-      return r * nkz + k;
+      return r * (a.xpitch ? a.xpitch : nkz) + k;
     }
   };
 
@@ -1923,13 +1928,15 @@ inline bool zdma_enabled() {
   }();
   return on;
 }
-// the slot's 16-byte copies need every row of every field to start at a 16-byte boundary: nkz even
-// (rows start at multiples of nkz), the field stride even and the base aligned; and a row's byte
-// offset plus one field stride fits 32 bits (zphys_kernel slot_issue reaches into the next field)
+// the slot's 16-byte copies need every row of every field to start at a 16-byte boundary: nkz and
+// the row pitch even (rows start at multiples of the pitch), the field stride even and the base
+// aligned; and a row's byte offset plus one field stride fits 32 bits (zphys_kernel slot_issue
+// reaches into the next field)
 inline bool zdma_ok(const ZArgs& a, const void* fields) {
   const unsigned long long rows = static_cast<unsigned long long>(a.ny) * a.NX;
-  return a.nkz % 2 == 0 && a.field_stride % 2 == 0 && reinterpret_cast<uintptr_t>(fields) % 16 == 0 &&
-         a.field_stride > 0 && (static_cast<unsigned long long>(a.field_stride) + rows * a.nkz) * 8 < (1ull << 32) && zdma_enabled();
+  const int pitch = a.xpitch ? a.xpitch : a.nkz;
+  return a.nkz % 2 == 0 && pitch % 2 == 0 && a.field_stride % 2 == 0 && reinterpret_cast<uintptr_t>(fields) % 16 == 0 &&
+         a.field_stride > 0 && (static_cast<unsigned long long>(a.field_stride) + rows * pitch) * 8 < (1ull << 32) && zdma_enabled();
 }
 
 // The template arguments of this thread's last z-stage launch, as in the rocprofv3 kernel names
@@ -1937,7 +1944,7 @@ inline bool zdma_ok(const ZArgs& a, const void* fields) {
 // recorded like xfft_note_variant and formatted only when asked for (zphys_last_variant)
 struct ZVariant {
   int nn = 0, tpr = 0, zr = 0, wpe = 0, zf = 0;
-  bool f64 = false, seg = false, zh = false, dma = false;
+  bool f64 = false, seg = false, zh = false, dma = false, xp = false;
 };
 ZVariant& zphys_variant_slot();
 
@@ -1947,25 +1954,31 @@ static void zphys_launch_tpr(const ZArgs& a, void* fields, const Twiddles& tw, h
   constexpr int ZR = zphys_rows<NN, T, TPR>();
   const long long nrows = static_cast<long long>(a.ny) * a.NX;
   // (one segment with 32-bit byte offsets when a field's rows fit 4 GiB; the segment path otherwise)
+  const bool xp = a.xpitch != 0;  // (zphys: then xexp_pitch(nkz), one segment of all retained kz)
   const bool seg = a.nseg > 1 || a.nkz != NN / 3 + 1 ||
-                   static_cast<unsigned long long>(nrows) * a.nkz * sizeof(T2) >= (1ull << 32);
+                   static_cast<unsigned long long>(nrows) * (xp ? a.xpitch : a.nkz) * sizeof(T2) >= (1ull << 32);
+  CH_CHECK(!(seg && xp), "zphys: a field's padded rows exceed 4 GiB (use smaller y chunks)");
   auto kern = seg ? (zh ? zphys_kernel<NN, T, true, true, TPR, ZR, WPE> : zphys_kernel<NN, T, true, false, TPR, ZR, WPE>)
-                  : (zh ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE> : zphys_kernel<NN, T, false, false, TPR, ZR, WPE>);
+              : xp ? (zh ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 3, false, true>
+                         : zphys_kernel<NN, T, false, false, TPR, ZR, WPE, 3, false, true>)
+                   : (zh ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE> : zphys_kernel<NN, T, false, false, TPR, ZR, WPE>);
   int zfv = 3;
   bool dma = false;
   if constexpr (sizeof(T) == 4 && NN == 1024 && TPR == 64 && WPE == 2) {
     const int zf = zfft_mode();
-    if (!seg && zh && zf == 0) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 0>;
-    if (!seg && zh && zf == 1) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 1>;
-    if (!seg && zh && zf == 2) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 2>;
-    if (!seg && zh && zf == 4) kern = zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4>;
+    if (!seg && zh && zf == 0) kern = xp ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 0, false, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 0>;
+    if (!seg && zh && zf == 1) kern = xp ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 1, false, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 1>;
+    if (!seg && zh && zf == 2) kern = xp ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 2, false, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 2>;
+    if (!seg && zh && zf == 4) kern = xp ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4, false, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4>;
     if (!seg && zh && zf >= 0 && zf <= 4 && zf != 3) zfv = zf;
     // ZF >= 3: pair 1 of the next row through the per-wave LDS slot where the rows are whole
     // 16-byte pieces; the register-only prefetch otherwise
     dma = !seg && zh && zfv >= 3 && zdma_ok(a, fields);
-    if (dma) kern = zfv == 4 ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 3, true>;
+    if (dma)
+      kern = zfv == 4 ? (xp ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4, true, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 4, true>)
+                      : (xp ? zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 3, true, true> : zphys_kernel<NN, T, false, true, TPR, ZR, WPE, 3, true>);
   }
-  zphys_variant_slot() = ZVariant{NN, TPR, ZR, WPE, zfv, sizeof(T) == 8, seg, zh, dma};
+  zphys_variant_slot() = ZVariant{NN, TPR, ZR, WPE, zfv, sizeof(T) == 8, seg, zh, dma, xp};
   const long long ngroups = (nrows + ZR - 1) / ZR;
   const long long cap = zpers_enabled() ? persist_blocks(reinterpret_cast<const void*>(kern), ZR * TPR, "CHANNEL_Z_BPC") : ngroups;
   dim3 grid(static_cast<unsigned>(std::min(ngroups, cap)));
@@ -2097,6 +2110,7 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
   const bool rv = HIST ? bx + w < a.NX : r < nrows;
   const long long rc = rv ? r : (HIST ? rfirst : nrows - 1);
   const int yl = static_cast<int>(rc / a.NX), pl0 = static_cast<int>(rfirst / a.NX);
+  const long long rowp = a.xpitch ? a.xpitch : nkz;  // row pitch of the x-expanded inputs and of spec_out
   const double Uy = (PRES || HIST || a.moments) ? a.U[a.y0 + yl] : 0.0;
   const int hb2 = HIST ? a.nb + 2 : 1, jb2 = HIST ? a.nj + 2 : 1;
   const unsigned jmag = HIST ? ((1u << 20) + a.nb / a.nj - 1) / (a.nb / a.nj) : 0u;
@@ -2105,8 +2119,8 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
     const bool tv = a.triple && p == 1;  // triple products: w pairs with v (the host checks nfields == 3)
     const int fa = 2 * p, fb = tv ? 1 : 2 * p + 1;
     const bool hb = tv || fb < a.nfields;  // an odd field count: the last field pairs with zero
-    const T2* A = fields + fa * a.field_stride + rc * nkz;
-    const T2* B = fields + (hb ? fb : fa) * a.field_stride + rc * nkz;
+    const T2* A = fields + fa * a.field_stride + rc * rowp;
+    const T2* B = fields + (hb ? fb : fa) * a.field_stride + rc * rowp;
     // unconditional loads at a clamped (in-bounds) index, zeros selected afterwards; Z_k = A_k + i B_k,
     // Z_{N-k} = conj(A_k) + i conj(B_k), the kz = 0 imaginary parts dropped, zeros between
 #pragma unroll
@@ -2289,7 +2303,7 @@ __global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(
           row_sync<TPRF>();  // the row's (r, 0) are in place
           wave_fft<NZP, RWW, PITCH, false, TPRF>(frow, tws, ft);
           const T sc = static_cast<T>(1.0 / (static_cast<double>(a.NX) * NZP));
-          T2* O = static_cast<T2*>(a.spec_out) + rc * nkz;
+          T2* O = static_cast<T2*>(a.spec_out) + rc * rowp;
 #pragma unroll
           for (int i = 0; i < MK; ++i) {
             const int k = t + TPR * i;
