@@ -174,6 +174,21 @@ class ChannelFlow:
         d["kz"] = 2.0 * np.pi / self.cfg.LZ * np.arange(d["ekz"].shape[-1])
         return d
 
+    def spectral_budgets(self) -> dict:
+        """Spectral Reynolds-stress budget terms of the current state at every plane
+        (``statistics.SBUDGET_ROWS``; ``reference.spectral_budgets`` has the equations): ``ekx``
+        ``(20, NY, Kx + 1)`` by |kx| and ``ekz`` ``(20, NY, nkz)`` by kz with the conventions of
+        ``plane_spectra``, the wavenumbers ``kx`` and ``kz``, and the mean profile ``U`` and its compact
+        derivative ``dU`` as the rows used them.  One rank without a communicator; the run is not
+        disturbed."""
+        d = dict(self.solver.spectral_budgets())
+        for k in ("ekx", "ekz", "U", "dU"):
+            d[k] = np.asarray(d[k])
+        d["rows"] = list(d["rows"])
+        d["kx"] = 2.0 * np.pi / self.cfg.LX * np.arange(d["ekx"].shape[-1])
+        d["kz"] = 2.0 * np.pi / self.cfg.LZ * np.arange(d["ekz"].shape[-1])
+        return d
+
     def plane_histograms(self, planes=None, nbins: int = 128, njoint: int = 64, span: float = 8.0,
                          vorticity: bool = False, centre=None, halfwidth=None) -> dict:
         """Histograms of u, v, w (``vorticity``: and wx, wy, wz) of the current state at the distinct y
@@ -206,7 +221,7 @@ class ChannelFlow:
     def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False,
                           pressure: bool = False, pressure_strain: bool = False, spectra: bool = False,
                           spectra_pressure: bool = False, pdfs: bool = False, pdf_planes=None, pdf_bins: int = 128,
-                          pdf_span: float = 8.0, pdf_vorticity: bool = False):
+                          pdf_span: float = 8.0, pdf_vorticity: bool = False, spectral_budgets: bool = False):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
         ``moments``: also the third and fourth central moments (skewness / flatness profiles);
@@ -220,7 +235,9 @@ class ChannelFlow:
         ``pdfs``: also the histograms at ``pdf_planes`` (default: every plane) with ``pdf_bins`` bins over
         ``pdf_span`` r.m.s. either side, with the vorticity when ``pdf_vorticity``
         (``TurbulenceStatistics.pdfs``; one rank).  The first sample's centres and half-widths bin every
-        later sample."""
+        later sample.
+        ``spectral_budgets``: also the spectral budget rows with the stress spectra they go with
+        (``TurbulenceStatistics.spectral_budgets``; one rank)."""
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -243,6 +260,9 @@ class ChannelFlow:
                 if spectra:
                     sp = self.plane_spectra(spectra_pressure)
                     self.statistics.add_spectra(sp["ekx"], sp["ekz"], sp["kx"], sp["kz"], self.cfg.NX, 2 * self.cfg.NZ - 2)
+                if spectral_budgets:
+                    sb, sp = self.spectral_budgets(), self.plane_spectra()
+                    self.statistics.add_spectral_budgets(sb["ekx"], sb["ekz"], sp["ekx"][:4], sp["ekz"][:4], sb["kx"], sb["kz"])
                 if pdfs:
                     c, hw = self.statistics.pdf_frozen() or (None, None)
                     self.statistics.add_histograms(self.plane_histograms(pdf_planes, pdf_bins, math.gcd(int(pdf_bins), 64),

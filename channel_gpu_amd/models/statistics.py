@@ -17,7 +17,9 @@ sums of the spectral static pressure (``Solver.pressure_strain``) into the press
 which the uu, vv, ww and uv budgets close component by component.  The one-dimensional spectra at
 every plane (``Solver.plane_spectra``) are averaged into wall-unit spectra, premultiplied spectra and
 two-point correlations (``spectra``).  The per-plane histograms (``Solver.plane_histograms``) are summed
-into PDFs, the joint PDF of (u', v) and the quadrant split of -u'v' (``pdfs``).
+into PDFs, the joint PDF of (u', v) and the quadrant split of -u'v' (``pdfs``).  The spectral budget rows
+(``Solver.spectral_budgets``) are averaged into the terms of the uu, vv, ww and uv budgets per (y, k)
+(``spectral_budgets``).
 """
 from __future__ import annotations
 
@@ -43,6 +45,12 @@ PSTRAIN_TERMS = ("pstrain_uu", "pstrain_vv", "pstrain_ww", "pstrain_uv")
 # rows of Solver.plane_spectra(): |u|^2, |v|^2, |w|^2, Re(u v*), |omega_x|^2, |omega_y|^2, |omega_z|^2,
 # |p'|^2 per |kx| and per kz at every plane
 SPECTRA_ROWS = ("uu", "vv", "ww", "uv", "wxwx", "wywy", "wzwz", "pp")
+# rows of Solver.spectral_budgets() per |kx| and per kz at every plane (reference/spectral_budgets.py)
+SBUDGET_ROWS = ("n_uu", "n_vv", "n_ww", "n_uv", "g_uu", "g_vv", "g_ww", "g_uv", "gs_uu", "gs_vv", "gs_ww", "gs_uv",
+                "gu", "gv", "ps_uu", "ps_vv", "ps_ww", "ps_uv", "pu", "pv")
+SBUDGET_STRESSES = ("uu", "vv", "ww", "uv")
+SBUDGET_TERMS = ("production", "nonlinear", "pressure_strain", "pressure_diffusion", "viscous_diffusion", "dissipation",
+                 "residual")
 
 
 class TurbulenceStatistics:
@@ -73,6 +81,8 @@ class TurbulenceStatistics:
         self.nsp = 0
         self.ekx = self.ekz = self.kx = self.kz = None
         self.nxz = (0, 0)
+        self.nsb = 0
+        self.sb_kx = self.sb_kz = self.sb_ekx = self.sb_ekz = self.sb_k = None
         self.nh = 0
         self.hist = self.joint = self.quad = None
         self.h_planes = self.h_names = self.h_centre = self.h_halfwidth = None
@@ -220,6 +230,69 @@ class TurbulenceStatistics:
                 out[f"premult_k{d}"][row] = idx * a
                 if row in AUTO_ROWS:
                     out[f"R_{d}"][row] = correlations(a, nn)
+        return out
+
+    def add_spectral_budgets(self, bkx, bkz, ekx, ekz, kx, kz):
+        """One sample of the spectral budget rows (``Solver.spectral_budgets``): ``bkx`` [20, NY, nkx] by
+        |kx| and ``bkz`` [20, NY, nkz] by kz (``SBUDGET_ROWS``), with the stress spectra uu, vv, ww, uv of
+        the same state, ``ekx`` [4, NY, nkx] and ``ekz`` [4, NY, nkz] (rows 0..3 of
+        ``Solver.plane_spectra``), and the wavenumbers in solver units."""
+        n = self.y.size
+        bkx, bkz, ekx, ekz = (np.asarray(a, float) for a in (bkx, bkz, ekx, ekz))
+        if bkx.shape[:2] != (len(SBUDGET_ROWS), n) or bkz.shape[:2] != (len(SBUDGET_ROWS), n):
+            raise ValueError(f"budget rows of shape {bkx.shape}, {bkz.shape}: expected ({len(SBUDGET_ROWS)}, {n}, nk)")
+        if ekx.shape != (4, n, bkx.shape[2]) or ekz.shape != (4, n, bkz.shape[2]):
+            raise ValueError(f"stress spectra of shape {ekx.shape}, {ekz.shape}: expected (4, {n}, nk) with the rows' nk")
+        if self.nsb == 0:
+            self.sb_kx, self.sb_kz = np.zeros_like(bkx), np.zeros_like(bkz)
+            self.sb_ekx, self.sb_ekz = np.zeros_like(ekx), np.zeros_like(ekz)
+            self.sb_k = (np.asarray(kx, float).copy(), np.asarray(kz, float).copy())
+        self.sb_kx += bkx
+        self.sb_kz += bkz
+        self.sb_ekx += ekx
+        self.sb_ekz += ekz
+        self.nsb += 1
+
+    def spectral_budgets(self) -> dict:
+        """Averaged terms of the uu, vv, ww and uv budgets per (y, k), folded onto the lower half, in wall
+        units (u_tau^4 / nu per wavenumber bin).  Two-dimensional, so kept out of ``profiles``:
+
+          y_plus                              [h]      from the nearest wall
+          kx_plus, kz_plus                    [nk]     k nu / u_tau
+          lambda_x_plus, lambda_z_plus        [nk]     2 pi / k+ (inf at k = 0)
+          terms_kx[stress][term], terms_kz..  [h, nk]  ``SBUDGET_TERMS`` of ``SBUDGET_STRESSES``
+          premult_kx[stress][term], premult_kz..       (k / dk) times the term, as ``spectra`` does
+
+        production -2 U' E_uv (uu), -U' E_vv (uv); nonlinear: turbulent transport plus inter-scale transfer;
+        pressure_strain; pressure_diffusion -2 D1 pv (vv), -D1 pu (uv); viscous_diffusion nu D2 E;
+        dissipation -2 nu g; residual: minus their sum, the unsteadiness of the finite average.  Summed over
+        k the terms are those of ``budgets`` and ``pressure_terms``.  U is the average of ``add``; every term
+        of uu, vv, ww is folded symmetrically and every term of uv antisymmetrically, like ``profiles``."""
+        if self.nsb == 0 or self.n == 0:
+            raise ValueError("no spectral budget samples")
+        from ..reference.spectral_budgets import budget_terms
+
+        ops = self._ops()
+        n = self.y.size
+        ut, nu = self.utau(), self.nu
+        U = self.U / self.n
+        h = (n + 1) // 2
+        lo = np.arange(h)
+        hi = n - 1 - lo
+        sc = nu / ut ** 4
+        out = {"y_plus": (1.0 + self.y[lo]) * ut / nu, "terms_kx": {}, "terms_kz": {}, "premult_kx": {}, "premult_kz": {}}
+        for d, k, rows, e in (("x", self.sb_k[0], self.sb_kx / self.nsb, self.sb_ekx / self.nsb),
+                              ("z", self.sb_k[1], self.sb_kz / self.nsb, self.sb_ekz / self.nsb)):
+            out[f"k{d}_plus"] = k * nu / ut
+            with np.errstate(divide="ignore"):
+                out[f"lambda_{d}_plus"] = 2.0 * np.pi / out[f"k{d}_plus"]
+            idx = k / k[1] if k.size > 1 else np.zeros_like(k)
+            for s, terms in budget_terms(ops, nu, U, rows, e).items():
+                terms["residual"] = -sum(terms.values())
+                sign = -1.0 if s == "uv" else 1.0
+                folded = {t: sc * 0.5 * (a[lo] + sign * a[hi]) for t, a in terms.items()}
+                out[f"terms_k{d}"][s] = folded
+                out[f"premult_k{d}"][s] = {t: idx * a for t, a in folded.items()}
         return out
 
     def add_pressure_strain(self, ps):

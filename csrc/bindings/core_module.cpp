@@ -100,7 +100,7 @@ PYBIND11_MODULE(_core, m) {
       RW(ic) RW(ic_amplitude) RW(forcing) RW(influence) RW(explicit_d2) RW(checkpoint_async) RW(health_check) RW(health_every) RW(on_nan) RW(snapshot_every)
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
       RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every)
-      RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure)
+      RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure) RW(sbudget_every)
       RW(pdf_every) RW(pdf_planes) RW(pdf_bins) RW(pdf_joint_bins) RW(pdf_span) RW(pdf_vorticity);
 #undef RW
 
@@ -380,7 +380,49 @@ PYBIND11_MODULE(_core, m) {
            py::arg("pressure") = false,
            "1-D spectra and co-spectra uu, vv, ww, uv, wxwx, wywy, wzwz, pp of the current state at every plane: ekx "
            "(8, NY, Kx+1) by |kx|, ekz (8, NY, nkz) by kz, global over the communicator; row pp is zero unless "
-           "pressure (one rank)");
+           "pressure (one rank)")
+      .def("spectral_budgets",
+           [](Solver& s) {
+             // the arrays view the result in place (a capsule owns it): no second host copy
+             auto sb = std::make_unique<Solver::SpectralBudgets>();
+             {
+               py::gil_scoped_release r;
+               *sb = s.spectral_budgets();
+             }
+             Solver::SpectralBudgets* raw = sb.release();
+             py::capsule owner(raw, [](void* q) { delete static_cast<Solver::SpectralBudgets*>(q); });
+             const Plan& p = s.plan();
+             auto arr = [&](std::vector<double>& v, int nk) {
+               return py::array_t<double>({static_cast<py::ssize_t>(kSBudRows), static_cast<py::ssize_t>(p.NY),
+                                           static_cast<py::ssize_t>(nk)}, v.data(), owner);
+             };
+             py::dict d;
+             d["rows"] = raw->rows;
+             d["ekx"] = arr(raw->ekx, p.Kx + 1);
+             d["ekz"] = arr(raw->ekz, p.nkz);
+             d["U"] = py::array_t<double>({static_cast<py::ssize_t>(p.NY)}, raw->U.data(), owner);
+             d["dU"] = py::array_t<double>({static_cast<py::ssize_t>(p.NY)}, raw->dU.data(), owner);
+             return d;
+           },
+           "spectral Reynolds-stress budget terms of the current state at every plane, rows n_uu n_vv n_ww n_uv g_uu g_vv "
+           "g_ww g_uv gs_uu gs_vv gs_ww gs_uv gu gv ps_uu ps_vv ps_ww ps_uv pu pv: ekx (20, NY, Kx+1) by |kx|, ekz "
+           "(20, NY, nkz) by kz, and the mean profile U and its derivative dU as used (one rank)")
+      .def("spectral_budgets_timing", &Solver::spectral_budgets_timing, py::call_guard<py::gil_scoped_release>(),
+           "device ms of the two stages of one spectral_budgets(): [rows 0..7, rows 8..19] (one rank)")
+      .def("rotational_hat",
+           [](Solver& s) {
+             std::vector<std::complex<double>> v;
+             {
+               py::gil_scoped_release r;
+               v = s.rotational_hat();
+             }
+             const Plan& p = s.plan();
+             py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(3), static_cast<py::ssize_t>(p.NY),
+                                                  static_cast<py::ssize_t>(p.nkx_loc), static_cast<py::ssize_t>(p.nkz_loc)});
+             std::copy(v.begin(), v.end(), a.mutable_data());
+             return a;
+           },
+           "H = (u x omega)^ of the current state per (kx, kz) line, (3, NY, nkx, nkz) (one rank)");
 
   py::class_<ProcInfo>(m, "ProcInfo")
       .def(py::init<>())

@@ -231,6 +231,7 @@ Config Config::from_tree(const ConfigTree& t) {
   c.pstrain_every = static_cast<int>(t.get_int(pick(t, "pstrain_every"), c.pstrain_every));
   c.yspectra_every = static_cast<int>(t.get_int(pick(t, "yspectra_every"), c.yspectra_every));
   c.yspectra_pressure = static_cast<int>(t.get_int(pick(t, "yspectra_pressure"), c.yspectra_pressure));
+  c.sbudget_every = static_cast<int>(t.get_int(pick(t, "sbudget_every"), c.sbudget_every));
   c.pdf_every = static_cast<int>(t.get_int(pick(t, "pdf_every"), c.pdf_every));
   c.pdf_planes = t.get_string(pick(t, "pdf_planes"), c.pdf_planes);
   c.pdf_bins = static_cast<int>(t.get_int(pick(t, "pdf_bins"), c.pdf_bins));
@@ -341,7 +342,8 @@ void Config::validate() const {
            "ic must be random|laminar|file|os_mode|zero");
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
                spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
-               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0 && yspectra_every >= 0 && pdf_every >= 0,
+               budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0 && yspectra_every >= 0 && pdf_every >= 0 &&
+               sbudget_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(yspectra_pressure == 0 || yspectra_pressure == 1, "yspectra_pressure must be 0|1");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
@@ -393,6 +395,7 @@ std::string Config::to_string() const {
   o << "  pressure_every = " << pressure_every << ";\n";
   o << "  pstrain_every = " << pstrain_every << ";\n";
   o << "  yspectra_every = " << yspectra_every << ";\n  yspectra_pressure = " << yspectra_pressure << ";\n";
+  o << "  sbudget_every = " << sbudget_every << ";\n";
   o << "  pdf_every = " << pdf_every << ";\n  pdf_planes = \"" << pdf_planes << "\";\n";
   o << "  pdf_bins = " << pdf_bins << ";\n  pdf_joint_bins = " << pdf_joint_bins << ";\n";
   o << "  pdf_span = " << pdf_span << ";\n  pdf_vorticity = " << pdf_vorticity << ";\n";

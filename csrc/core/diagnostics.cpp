@@ -76,6 +76,17 @@ std::string npy_header(const char* descr, const std::string& shape) {
   return h + dict;
 }
 
+// float64 rows per plane and wavenumber, (rows, ny, nk), as a NumPy file (YSPEC_*, SBUD_*)
+void write_rows_npy(const std::string& fn, const std::vector<double>& v, int rows, int ny, int nk) {
+  std::ofstream f(fn, std::ios::binary | std::ios::trunc);
+  CH_CHECK(f.good(), "cannot open '" << fn << "'");
+  const std::string h = npy_header("<f8", "(" + std::to_string(rows) + ", " + std::to_string(ny) + ", " + std::to_string(nk) + ")");
+  f.write(h.data(), static_cast<std::streamsize>(h.size()));
+  f.write(reinterpret_cast<const char*>(v.data()), static_cast<std::streamsize>(v.size() * sizeof(double)));
+  f.close();
+  CH_CHECK(!f.fail(), "writing '" << fn << "' failed");
+}
+
 // The export passes of a field selection (phys_field_index values): one pass of the six physical-stage
 // fields, or, with p, a pressure-mode pass (u, v, w and Pi, which takes field slot 3) that also serves
 // u, v, w, and a plain pass for any of wx, wy, wz beside it.
@@ -623,19 +634,41 @@ void Solver::write_pdf_files() {
 // what it would have seen.  phys_ is scratch between steps, as the export assumes.
 void Solver::pressure_device(double* ms) {
   CH_CHECK(!comm_, "pressure: the pressure solve is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
   if (!prepared_) prepare();
-  if (!d_pres_) {
-    HIP_CHECK(hipMalloc(&d_pres_, 3 * spec_ * esz_));
-    HIP_CHECK(hipMemsetAsync(d_pres_, 0, 3 * spec_ * esz_, s_comp_));
-  }
   hipEvent_t te[3] = {nullptr, nullptr, nullptr};
   if (ms) {
     for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(hipEventRecord(te[0], s_comp_));
   }
-  transforms(1, false, d_pres_);
+  rotational_device();
   if (ms) HIP_CHECK(hipEventRecord(te[1], s_comp_));
+  poisson_device();
+  if (ms) {
+    HIP_CHECK(hipEventRecord(te[2], s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    float t01 = 0, t12 = 0;
+    HIP_CHECK(hipEventElapsedTime(&t01, te[0], te[1]));
+    HIP_CHECK(hipEventElapsedTime(&t12, te[1], te[2]));
+    ms[0] = t01;
+    ms[1] = t12;
+    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+  }
+}
+
+// the first half: H = (u x omega)^ of the current state into the three fields of d_pres_
+void Solver::rotational_device() {
+  CH_CHECK(!comm_, "pressure: the pressure solve is single-rank (a solver without a communicator)");
+  if (!prepared_) prepare();
+  if (!d_pres_) {
+    HIP_CHECK(hipMalloc(&d_pres_, 3 * spec_ * esz_));
+    HIP_CHECK(hipMemsetAsync(d_pres_, 0, 3 * spec_ * esz_, s_comp_));
+  }
+  transforms(1, false, d_pres_);
+}
+
+// the second half: the y-line Poisson solve, Pi in place over H_x
+void Solver::poisson_device() {
+  const Plan& p = plan_;
   PressureArgs a;
   a.N = p.NY;
   a.lines = p.nkx_loc * nkzs_;
@@ -656,16 +689,17 @@ void Solver::pressure_device(double* ms) {
   a.phi = field_ptr(PHI);
   a.pi = h;
   pressure_solve(ytab_, a, fp64_, s_comp_);
-  if (ms) {
-    HIP_CHECK(hipEventRecord(te[2], s_comp_));
-    HIP_CHECK(hipStreamSynchronize(s_comp_));
-    float t01 = 0, t12 = 0;
-    HIP_CHECK(hipEventElapsedTime(&t01, te[0], te[1]));
-    HIP_CHECK(hipEventElapsedTime(&t12, te[1], te[2]));
-    ms[0] = t01;
-    ms[1] = t12;
-    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+}
+
+std::vector<std::complex<double>> Solver::rotational_hat() {
+  rotational_device();
+  std::vector<std::complex<double>> out;
+  out.reserve(3 * canon_);
+  for (int c = 0; c < 3; ++c) {
+    const std::vector<std::complex<double>> h = spec_to_canonical(static_cast<const char*>(d_pres_) + c * spec_ * esz_, "rotational term");
+    out.insert(out.end(), h.begin(), h.end());
   }
+  return out;
 }
 
 std::vector<double> Solver::pressure_timing() {
@@ -750,8 +784,13 @@ void Solver::write_pressure_files() {
 // stays the zeros of the allocation.  Like the export it writes nothing the next step reads.
 void Solver::static_pressure_device() {
   CH_CHECK(!comm_, "static_pressure: the export is single-rank (a solver without a communicator)");
-  const Plan& p = plan_;
   pressure_device();
+  static_return_device();
+}
+
+// the second half: from Pi in field 0 of d_pres_ to p-hat' in field 1
+void Solver::static_return_device() {
+  const Plan& p = plan_;
   const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
   XArgs xa = x_args();
   const XSrc src = x_src_local(xa);
@@ -868,18 +907,8 @@ void Solver::write_yspectra_files() {
   const Plan& p = plan_;
   char step[16];
   std::snprintf(step, sizeof(step), "%08ld", nstep_);
-  auto put = [&](const char* name, const std::vector<double>& v, int nk) {
-    const std::string fn = cfg_.path + name + step + ".npy";
-    std::ofstream f(fn, std::ios::binary | std::ios::trunc);
-    CH_CHECK(f.good(), "cannot open '" << fn << "'");
-    const std::string h = npy_header("<f8", "(" + std::to_string(kYSpecRows) + ", " + std::to_string(p.NY) + ", " + std::to_string(nk) + ")");
-    f.write(h.data(), static_cast<std::streamsize>(h.size()));
-    f.write(reinterpret_cast<const char*>(v.data()), static_cast<std::streamsize>(v.size() * sizeof(double)));
-    f.close();
-    CH_CHECK(!f.fail(), "writing '" << fn << "' failed");
-  };
-  put("YSPEC_KX_", sp.ekx, p.Kx + 1);
-  put("YSPEC_KZ_", sp.ekz, p.nkz);
+  write_rows_npy(cfg_.path + "YSPEC_KX_" + step + ".npy", sp.ekx, kYSpecRows, p.NY, p.Kx + 1);
+  write_rows_npy(cfg_.path + "YSPEC_KZ_" + step + ".npy", sp.ekz, kYSpecRows, p.NY, p.nkz);
   std::ofstream js(cfg_.path + "YSPEC_" + step + ".json");
   js.precision(17);
   js << "{\"step\": " << nstep_ << ", \"time\": " << time() << ", \"rows\": [";
@@ -887,6 +916,106 @@ void Solver::write_yspectra_files() {
   js << "], \"pressure\": " << (pres ? "true" : "false") << ", \"ax\": " << p.ax << ", \"az\": " << p.az << ", \"y\": [";
   for (int j = 0; j < p.NY; ++j) js << (j ? ", " : "") << grid_.y[j];
   js << "], \"Re\": " << cfg_.Re << "}\n";
+}
+
+// ---- spectral Reynolds-stress budgets ------------------------------------------------------------
+// The two halves of the pressure and of the static pressure with a stage of the reduction after each:
+// rows 0..7 while d_pres_ holds H, rows 8..19 once it holds Pi (field 0) and p-hat' (field 1).  U' is the
+// host's compact D1 of the mean profile.  Like the pressure it writes d_pres_, the step's scratch and
+// its own sums only.
+Solver::SpectralBudgets Solver::spectral_budgets(double* ms) {
+  CH_CHECK(!comm_, "spectral_budgets: the pressure solve is single-rank (a solver without a communicator)");
+  const Plan& p = plan_;
+  const size_t nx = static_cast<size_t>(kSBudRows) * p.NY * (p.Kx + 1), nz = static_cast<size_t>(kSBudRows) * p.NY * p.nkz;
+  const size_t N = static_cast<size_t>(p.NY);
+  if (!d_sbud_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_sbud_), (nx + nz + 2 * N) * sizeof(double)));
+  if (!h_sbud_) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_sbud_), (nx + nz) * sizeof(double), hipHostMallocDefault));
+  if (!prepared_) prepare();
+  SpectralBudgets out;
+  out.rows = {"n_uu", "n_vv", "n_ww", "n_uv", "g_uu", "g_vv", "g_ww", "g_uv", "gs_uu", "gs_vv",
+              "gs_ww", "gs_uv", "gu", "gv", "ps_uu", "ps_vv", "ps_ww", "ps_uv", "pu", "pv"};
+  out.U = mean_profile();
+  out.dU = d1_profile(grid_, out.U);
+  std::vector<double> prof(out.U);
+  prof.insert(prof.end(), out.dU.begin(), out.dU.end());
+  HIP_CHECK(hipMemsetAsync(d_sbud_, 0, (nx + nz) * sizeof(double), s_comp_));
+  HIP_CHECK(hipMemcpyAsync(d_sbud_ + nx + nz, prof.data(), 2 * N * sizeof(double), hipMemcpyHostToDevice, s_comp_));
+  HIP_CHECK(hipStreamSynchronize(s_comp_));  // (prof is pageable and leaves scope)
+  const size_t fsz = spec_ * esz_;
+  auto stage = [&](int st) {
+    SBudgetArgs a;
+    walk_args(a, st == 0 ? 63u : (1u | 2u | 4u | 32u), st == 1);
+    for (int c = 0; c < (st == 0 ? 3 : 1); ++c) a.h[c] = static_cast<const char*>(d_pres_) + c * fsz;
+    a.U = d_sbud_ + nx + nz;
+    a.dU = a.U + N;
+    a.stage = st;
+    a.nkz = p.nkz;
+    a.ekx = d_sbud_;
+    a.ekz = d_sbud_ + nx;
+    for_kblocks([&](size_t off, int cnt, int kx0) {
+      SBudgetArgs b = at_block(a, off, cnt, kx0);
+      for (const void*& q : b.h)
+        if (q) q = static_cast<const char*>(q) + off;
+      sbudget_accumulate(b, fp64_, s_comp_);
+    });
+  };
+  hipEvent_t te[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (ms)
+    for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
+  rotational_device();
+  if (ms) HIP_CHECK(hipEventRecord(te[0], s_comp_));
+  stage(0);
+  if (ms) HIP_CHECK(hipEventRecord(te[1], s_comp_));
+  poisson_device();
+  static_return_device();
+  if (ms) HIP_CHECK(hipEventRecord(te[2], s_comp_));
+  stage(1);
+  if (ms) HIP_CHECK(hipEventRecord(te[3], s_comp_));
+  reduce_fetch(d_sbud_, nx + nz, h_sbud_);
+  if (ms) {
+    float t01 = 0, t23 = 0;
+    HIP_CHECK(hipEventElapsedTime(&t01, te[0], te[1]));
+    HIP_CHECK(hipEventElapsedTime(&t23, te[2], te[3]));
+    ms[0] = t01;
+    ms[1] = t23;
+    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+  }
+  out.ekx.assign(h_sbud_, h_sbud_ + nx);
+  out.ekz.assign(h_sbud_ + nx, h_sbud_ + nx + nz);
+  return out;
+}
+
+std::vector<double> Solver::spectral_budgets_timing() {
+  std::vector<double> ms(2, 0.0);
+  spectral_budgets(ms.data());
+  return ms;
+}
+
+// <path>SBUD_KX_<step>.npy (20, NY, Kx+1) and <path>SBUD_KZ_<step>.npy (20, NY, nkz), float64, and a
+// sidecar <path>SBUD_<step>.json with the mean profile and its derivative as the rows used them
+void Solver::write_sbudget_files() {
+  if (comm_) return note_once(sbud_note_, plan_.rank,
+                              "[channel] sbudget_every: SBUD_KX_*.npy, SBUD_KZ_*.npy, SBUD_*.json skipped (the pressure solve is single-rank)\n");
+  const SpectralBudgets sb = spectral_budgets();
+  const Plan& p = plan_;
+  char step[16];
+  std::snprintf(step, sizeof(step), "%08ld", nstep_);
+  write_rows_npy(cfg_.path + "SBUD_KX_" + step + ".npy", sb.ekx, kSBudRows, p.NY, p.Kx + 1);
+  write_rows_npy(cfg_.path + "SBUD_KZ_" + step + ".npy", sb.ekz, kSBudRows, p.NY, p.nkz);
+  std::ofstream js(cfg_.path + "SBUD_" + step + ".json");
+  js.precision(17);
+  js << "{\"step\": " << nstep_ << ", \"time\": " << time() << ", \"rows\": [";
+  for (size_t k = 0; k < sb.rows.size(); ++k) js << (k ? ", " : "") << "\"" << sb.rows[k] << "\"";
+  js << "], \"ax\": " << p.ax << ", \"az\": " << p.az;
+  auto prof = [&](const char* key, const double* v) {
+    js << ", \"" << key << "\": [";
+    for (int j = 0; j < p.NY; ++j) js << (j ? ", " : "") << v[j];
+    js << "]";
+  };
+  prof("y", grid_.y.data());
+  prof("U", sb.U.data());
+  prof("dU", sb.dU.data());
+  js << ", \"Re\": " << cfg_.Re << "}\n";
 }
 
 // one line of NY values per call and file, as write_stats_files: the vorticity r.m.s., the

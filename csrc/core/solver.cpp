@@ -461,10 +461,13 @@ void Solver::free_all() {
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
                   static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
                   static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_),
-                  static_cast<void*>(d_yspec_), d_hist_})
+                  static_cast<void*>(d_yspec_), d_hist_, static_cast<void*>(d_sbud_)})
     if (p) (void)hipFree(p);
   d_pstr_ = nullptr;
   d_yspec_ = nullptr;
+  d_sbud_ = nullptr;
+  if (h_sbud_) (void)hipHostFree(h_sbud_);
+  h_sbud_ = nullptr;
   d_hist_ = nullptr;
   hist_n_ = 0;
   if (h_yspec_) (void)hipHostFree(h_yspec_);
@@ -2188,6 +2191,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (cfg_.pressure_every > 0 && nstep_ % cfg_.pressure_every == 0) write_pressure_files();
     if (cfg_.pstrain_every > 0 && nstep_ % cfg_.pstrain_every == 0) write_pstrain_files();
     if (cfg_.yspectra_every > 0 && nstep_ % cfg_.yspectra_every == 0) write_yspectra_files();
+    if (cfg_.sbudget_every > 0 && nstep_ % cfg_.sbudget_every == 0) write_sbudget_files();
     if (cfg_.pdf_every > 0 && nstep_ % cfg_.pdf_every == 0) write_pdf_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();

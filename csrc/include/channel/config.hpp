@@ -94,6 +94,7 @@ struct Config {
   int pressure_every = 0;              // 0 = off; pressure r.m.s. and pressure-velocity profiles (PRMS.dat, PU.dat, PV.dat; one rank)
   int pstrain_every = 0;               // 0 = off; pressure-strain profiles of the uu, vv, ww, uv budgets (PS_*.dat; one rank)
   int yspectra_every = 0;              // 0 = off; 1-D spectra and co-spectra at every plane (YSPEC_KX_<step>.npy, YSPEC_KZ_<step>.npy, YSPEC_<step>.json; any P)
+  int sbudget_every = 0;               // 0 = off; spectral Reynolds-stress budgets at every plane (SBUD_KX_<step>.npy, SBUD_KZ_<step>.npy, SBUD_<step>.json; one rank)
   int yspectra_pressure = 0;           // 1 = also the pressure row of those spectra (one rank)
   int pdf_every = 0;                   // 0 = off; histograms, joint (u, v) histogram and quadrant sums (PDF_<step>.npy, JPDF_UV_<step>.npy, QUAD_<step>.npy, PDF_<step>.json; one rank)
   std::string pdf_planes = "";         // comma-separated y indices ("" = every plane)

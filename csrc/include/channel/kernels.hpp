@@ -440,6 +440,30 @@ struct YSpectraArgs : SpecWalkArgs {  // all six fields; p or null
   double* ekz = nullptr;              // [kYSpecRows][N][nkz]
 };
 void yspectra_accumulate(const YSpectraArgs& a, bool fp64, hipStream_t s);
+// Spectral Reynolds-stress budgets at every plane: the terms of the uu, vv, ww, uv budgets per (y, |kx|)
+// and per (y, kz), accumulated (+=) like the spectra above (same walk, weights, masks and outputs, with
+// kSBudRows rows).  With a.b = Re(a b*), H' = H - H_lin the transform of u' x omega' (H = (u x omega)^,
+// H_lin = (-U' v, U' u - U omega_z, U omega_y)), G = Pi - U u the transform of p' + |u'|^2 / 2, p the
+// fluctuating static pressure and D the solver's own wall-normal derivatives (GradSumArgs), the rows are
+//    0..3   n_uu = u.H'x, n_vv = v.H'y, n_ww = w.H'z, n_uv = u.H'y + v.H'x
+//    4..7   g_uu, g_vv, g_ww, g_uv: the summands of the gradient sums' rows 3..6
+//    8..11  gs_uu = 2 G.(i al u), gs_vv = 2 G.Dv, gs_ww = 2 G.(i be w), gs_uv = G.(Du + i al v)
+//   12..13  gu = G.u, gv = G.v
+//   14..19  ps_uu, ps_vv, ps_ww, ps_uv, pu, pv: the summands of the pressure strain's rows 0..5
+// in two stages, because H and Pi share a buffer: stage 0 (rows 0..7) reads the six fields and h = H_x,
+// H_y, H_z; stage 1 (rows 8..19) reads u, v, w, omega_z, h[0] = Pi and p.
+constexpr int kSBudRows = 20;
+constexpr int kSBudStage0Rows = 8;    // rows of stage 0; stage 1 has the rest
+struct SBudgetArgs : SpecWalkArgs {
+  const void* h[3] = {};              // stage 0: H_x, H_y, H_z; stage 1: Pi (h[1], h[2] unused), in the layout of the fields
+  const double* U = nullptr;          // [N] mean profile
+  const double* dU = nullptr;         // [N] its wall-normal derivative (stage 0)
+  int stage = 0;
+  int nkz = 0;                        // global retained kz count
+  double* ekx = nullptr;              // [kSBudRows][N][Kx + 1]
+  double* ekz = nullptr;              // [kSBudRows][N][nkz]
+};
+void sbudget_accumulate(const SBudgetArgs& a, bool fp64, hipStream_t s);
 // element (local kx 0, kz 0) of every plane y < N of one spectral field (lines = nkx_loc * nkzs) := 0
 void zero_mean_line(void* q, int N, int kzb, int lines, bool fp64, hipStream_t s);
 // fault injection (tests): element `elem` of a complex field becomes NaN

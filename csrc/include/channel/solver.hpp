@@ -186,6 +186,20 @@ class Solver {
     std::vector<double> ekx, ekz;
   };
   PlaneSpectra plane_spectra(bool pressure = false);
+  // Spectral Reynolds-stress budgets of the current state at every plane (kernels.hpp SBudgetArgs): ekx
+  // [kSBudRows][NY][Kx+1] by |kx| and ekz [kSBudRows][NY][nkz] by kz, with the conventions of
+  // plane_spectra(); U and dU are the mean profile and its compact first derivative as the rows used
+  // them.  One rank without a communicator (it runs the pressure solve and the static pressure).
+  struct SpectralBudgets {
+    std::vector<std::string> rows;
+    std::vector<double> ekx, ekz, U, dU;
+  };
+  SpectralBudgets spectral_budgets(double* ms = nullptr);
+  // device time in ms of the launches of its two stages (events on the compute stream; tools/export_cost.py)
+  std::vector<double> spectral_budgets_timing();
+  // H = (u x omega)^ of the current state as the transform stage leaves it before the pressure solve:
+  // canonical [3][y][kx][kz] (one rank without a communicator)
+  std::vector<std::complex<double>> rotational_hat();
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -260,13 +274,19 @@ class Solver {
   void write_moment_files(const std::vector<double>& m);
   void write_budget_files();
   void write_pressure_files();
-  // Pi of the current state into field 0 of d_pres_ (device part of pressure_hat)
+  // Pi of the current state into field 0 of d_pres_ (device part of pressure_hat): H into the three
+  // fields of d_pres_ (rotational_device), then the y-line Poisson solve over H_x (poisson_device)
   void pressure_device(double* ms = nullptr);
+  void rotational_device();
+  void poisson_device();
   void write_pstrain_files();
   void write_pdf_files();
   void write_yspectra_files();
-  // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat)
+  void write_sbudget_files();
+  // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat): the
+  // pressure solve, then the return trip of r through physical space (static_return_device)
   void static_pressure_device();
+  void static_return_device();
   // one device spectral field as canonical [y][kx][kz]; refuses non-zero padding of the device layout
   std::vector<std::complex<double>> spec_to_canonical(const void* d_field, const char* what);
   // x-backward arguments of the whole local slab (transforms and the export): the common part, the
@@ -454,6 +474,9 @@ class Solver {
   double* d_yspec_ = nullptr;  // plane spectra: ekx [kYSpecRows][NY][Kx+1], then ekz [kYSpecRows][NY][nkz]
   double* h_yspec_ = nullptr;  // pinned host copy of d_yspec_ (the result is 17 MB at the headline grid)
   bool yspec_note_ = false;   // the "pressure row skipped" note has been printed
+  double* d_sbud_ = nullptr;  // spectral budgets: ekx [kSBudRows][NY][Kx+1], ekz [kSBudRows][NY][nkz], then U and dU [NY]
+  double* h_sbud_ = nullptr;  // pinned host copy of the sums of d_sbud_
+  bool sbud_note_ = false;    // the "spectral budget files skipped" note has been printed
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 
   bool use_graph_ = true;

@@ -1,8 +1,8 @@
 """Cost of one plane_moments(), one plane_histograms() without and with the vorticity, one gradient_sums(), one transport_moments(), one pressure solve (the
 device part of pressure_hat()), one pressure_moments(), one pressure_strain(), one plane_spectra() without and with
-the pressure row and one three-field all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
+the pressure row, one spectral_budgets() and one three-field all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
 --skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out; --pdfs-only stops after the
-histograms."""
+histograms; --sbudget-only runs the step, plane_spectra() and spectral_budgets() only."""
 import json
 import os
 import sys
@@ -27,6 +27,43 @@ for _ in range(10):
 s.synchronize()
 step_ms = (time.perf_counter() - t0) * 100.0
 res = {"grid": "1024x385x1024", "precision": "fp32", "step_ms": step_ms}
+
+def spectral_budget_cost():
+    """plane_spectra() and spectral_budgets(): host time of the whole calls, and the device time of the
+    launches of the two stages by events, against the bytes they read (stage 0: the six fields, or five in
+    the combine mode, and H_x, H_y, H_z; stage 1: u, v, w, omega_z, or the five, and Pi, p-hat')."""
+    nkx, nkz = 2 * (cfg.NX // 3) + 1, (2 * cfg.NZ - 2) // 3 + 1
+    nkzs = (nkz + 7) // 8 * 8 if s.spec_kzb() else nkz
+    field = cfg.NY * nkx * nkzs * 8
+    nf = 5 if s.combine() else 6
+    res["plane_spectra_bytes"] = nf * field
+    res["sbudget_stage0_bytes"] = (nf + 3) * field
+    res["sbudget_stage1_bytes"] = ((5 if s.combine() else 4) + 2) * field
+    res["sbudget_result_bytes"] = 20 * cfg.NY * (cfg.NX // 3 + 1 + nkz) * 8
+    for name, call in (("plane_spectra", s.plane_spectra), ("spectral_budgets", s.spectral_budgets)):
+        if name + "_ms" in res:  # (the full run has timed it above)
+            continue
+        ts = []
+        for rep in range(5):
+            t0 = time.perf_counter()
+            r = call()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        res[name + "_ms"] = ts
+        res[name + "_over_step"] = min(ts) / step_ms
+    tt = [s.spectral_budgets_timing() for _ in range(5)]
+    for st in (0, 1):
+        ms = [t[st] for t in tt]
+        res[f"sbudget_stage{st}_ms"] = ms
+        res[f"sbudget_stage{st}_TBps"] = res[f"sbudget_stage{st}_bytes"] / (min(ms) * 1e-3) / 1e12
+    g, ps = s.gradient_sums(), s.pressure_strain()
+    res["sbudget_g_uu_sum_vs_gradient_sums"] = float(abs(r["ekx"][4].sum(axis=-1) - g[3]).max() / abs(g[3]).max())
+    res["sbudget_ps_uu_sum_vs_pstrain"] = float(abs(r["ekz"][14].sum(axis=-1) - ps[0]).max() / abs(ps[0]).max())
+
+
+if "--sbudget-only" in sys.argv:
+    spectral_budget_cost()
+    print(json.dumps(res))
+    sys.exit(0)
 for rep in range(2):
     t0 = time.perf_counter()
     m = s.plane_moments()
@@ -122,6 +159,7 @@ for name, flag in (("plane_spectra", False), ("plane_spectra_pressure", True)):
 g = s.gradient_sums()
 res["plane_spectra_wxwx_sum_vs_gradient_sums"] = float(abs(sp["ekx"][4].sum(axis=-1) - g[0]).max() / abs(g[0]).max())
 res["plane_spectra_pp_sum_vs_pstrain"] = float(abs(sp["ekz"][7].sum(axis=-1) - ps[6]).max() / abs(ps[6]).max())
+spectral_budget_cost()
 if "--skip-fields" in sys.argv:
     print(json.dumps(res))
     sys.exit(0)
