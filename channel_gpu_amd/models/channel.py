@@ -174,6 +174,22 @@ class ChannelFlow:
         d["kz"] = 2.0 * np.pi / self.cfg.LZ * np.arange(d["ekz"].shape[-1])
         return d
 
+    def plane_cross_spectra(self, ref_planes, rows: str = "velocity") -> dict:
+        """Cross-spectra of every plane of the current state against the reference planes ``ref_planes``
+        (distinct y indices, at most 16) of the row set ``rows``: ``"velocity"`` (uu, vv, ww, uv) or
+        ``"shear"`` (u_wz, v_wz, w_wx, wz_wz), the first factor at y and the conjugated second at the
+        reference plane.  ``ckx`` ``(4, nref, NY, Kx + 1)`` by |kx| (conj(e) for kx < 0, summed over kz) and
+        ``ckz`` ``(4, nref, NY, nkz)`` by kz (summed over kx), complex, with the wavenumbers ``kx`` and ``kz``
+        and the grid ``y``; ``reference.cross_spectra`` has the definition and ``cross_correlations`` turns
+        the bins into correlation maps.  Any number of ranks; the run is not disturbed."""
+        d = dict(self.solver.plane_cross_spectra([int(j) for j in ref_planes], str(rows)))
+        d["ckx"], d["ckz"] = np.asarray(d["ckx"]), np.asarray(d["ckz"])
+        d["rows"], d["ref_planes"] = list(d["rows"]), list(d["ref_planes"])
+        d["kx"] = 2.0 * np.pi / self.cfg.LX * np.arange(d["ckx"].shape[-1])
+        d["kz"] = 2.0 * np.pi / self.cfg.LZ * np.arange(d["ckz"].shape[-1])
+        d["y"] = np.asarray(self.y)
+        return d
+
     def spectral_budgets(self) -> dict:
         """Spectral Reynolds-stress budget terms of the current state at every plane
         (``statistics.SBUDGET_ROWS``; ``reference.spectral_budgets`` has the equations): ``ekx``
@@ -221,7 +237,8 @@ class ChannelFlow:
     def sample_statistics(self, nsteps: int, every: int = 10, moments: bool = False, budgets: bool = False,
                           pressure: bool = False, pressure_strain: bool = False, spectra: bool = False,
                           spectra_pressure: bool = False, pdfs: bool = False, pdf_planes=None, pdf_bins: int = 128,
-                          pdf_span: float = 8.0, pdf_vorticity: bool = False, spectral_budgets: bool = False):
+                          pdf_span: float = 8.0, pdf_vorticity: bool = False, spectral_budgets: bool = False,
+                          cross_spectra: bool = False, cross_planes=None, cross_rows: str = "velocity"):
         """Advance ``nsteps`` steps, sampling U(y), the plane r.m.s. and <u'v'> (the reference's
         calcSt cadence, statistics.cu:161-243) every ``every`` steps into ``self.statistics``;
         ``moments``: also the third and fourth central moments (skewness / flatness profiles);
@@ -237,7 +254,12 @@ class ChannelFlow:
         (``TurbulenceStatistics.pdfs``; one rank).  The first sample's centres and half-widths bin every
         later sample.
         ``spectral_budgets``: also the spectral budget rows with the stress spectra they go with
-        (``TurbulenceStatistics.spectral_budgets``; one rank)."""
+        (``TurbulenceStatistics.spectral_budgets``; one rank).
+        ``cross_spectra``: also the cross-spectra of every plane against the reference planes ``cross_planes``
+        (required) of the row set ``cross_rows``, with the spectra of the same state for the normalisation
+        (``TurbulenceStatistics.cross_correlations``; any number of ranks)."""
+        if cross_spectra and not cross_planes:
+            raise ValueError("cross_spectra needs cross_planes, the reference y indices")
         done = 0
         while done < nsteps:
             k = min(every, nsteps - done)
@@ -263,6 +285,10 @@ class ChannelFlow:
                 if spectral_budgets:
                     sb, sp = self.spectral_budgets(), self.plane_spectra()
                     self.statistics.add_spectral_budgets(sb["ekx"], sb["ekz"], sp["ekx"][:4], sp["ekz"][:4], sb["kx"], sb["kz"])
+                if cross_spectra:
+                    cs, sp = self.plane_cross_spectra(cross_planes, cross_rows), self.plane_spectra()
+                    self.statistics.add_cross_spectra(cs["ckx"], cs["ckz"], cs["ref_planes"], cs["rows"], sp["ekx"], sp["ekz"],
+                                                      cs["kx"], cs["kz"], self.cfg.NX, 2 * self.cfg.NZ - 2)
                 if pdfs:
                     c, hw = self.statistics.pdf_frozen() or (None, None)
                     self.statistics.add_histograms(self.plane_histograms(pdf_planes, pdf_bins, math.gcd(int(pdf_bins), 64),

@@ -19,7 +19,9 @@ every plane (``Solver.plane_spectra``) are averaged into wall-unit spectra, prem
 two-point correlations (``spectra``).  The per-plane histograms (``Solver.plane_histograms``) are summed
 into PDFs, the joint PDF of (u', v) and the quadrant split of -u'v' (``pdfs``).  The spectral budget rows
 (``Solver.spectral_budgets``) are averaged into the terms of the uu, vv, ww and uv budgets per (y, k)
-(``spectral_budgets``).
+(``spectral_budgets``).  The cross-spectra of every plane against a few reference planes
+(``Solver.plane_cross_spectra``) are averaged into correlation maps around those planes, wall-normal
+correlation coefficients and linear coherence spectra (``cross_correlations``).
 """
 from __future__ import annotations
 
@@ -83,6 +85,9 @@ class TurbulenceStatistics:
         self.nxz = (0, 0)
         self.nsb = 0
         self.sb_kx = self.sb_kz = self.sb_ekx = self.sb_ekz = self.sb_k = None
+        self.ncs = 0
+        self.cs_kx = self.cs_kz = self.cs_ekx = self.cs_ekz = self.cs_k = self.cs_refs = self.cs_rows = None
+        self.cs_nxz = (0, 0)
         self.nh = 0
         self.hist = self.joint = self.quad = None
         self.h_planes = self.h_names = self.h_centre = self.h_halfwidth = None
@@ -293,6 +298,96 @@ class TurbulenceStatistics:
                 folded = {t: sc * 0.5 * (a[lo] + sign * a[hi]) for t, a in terms.items()}
                 out[f"terms_k{d}"][s] = folded
                 out[f"premult_k{d}"][s] = {t: idx * a for t, a in folded.items()}
+        return out
+
+    def add_cross_spectra(self, ckx, ckz, ref_planes, rows, ekx, ekz, kx, kz, nx: int | None = None, nz: int | None = None):
+        """One sample of the cross-spectra against reference planes (``Solver.plane_cross_spectra``):
+        ``ckx`` [4, nref, NY, nkx] and ``ckz`` [4, nref, NY, nkz], complex, of the planes ``ref_planes`` and
+        the row names ``rows``, with the spectra of the same state for the normalisation, ``ekx``
+        [8, NY, nkx] and ``ekz`` [8, NY, nkz] (``Solver.plane_spectra``), and the wavenumbers in solver
+        units.  ``nx``, ``nz``: the physical grid of the correlation maps (default: twice the highest
+        wavenumber index).  Every sample has the planes and rows of the first."""
+        ckx, ckz = np.asarray(ckx, complex), np.asarray(ckz, complex)
+        ekx, ekz = np.asarray(ekx, float), np.asarray(ekz, float)
+        refs, rows = [int(j) for j in ref_planes], [str(r) for r in rows]
+        n = self.y.size
+        if ckx.shape[:3] != (4, len(refs), n) or ckz.shape[:3] != (4, len(refs), n) or len(rows) != 4:
+            raise ValueError(f"cross-spectra of shape {ckx.shape}, {ckz.shape}: expected (4, {len(refs)}, {n}, nk)")
+        if ekx.shape != (len(SPECTRA_ROWS), n, ckx.shape[3]) or ekz.shape != (len(SPECTRA_ROWS), n, ckz.shape[3]):
+            raise ValueError(f"spectra of shape {ekx.shape}, {ekz.shape}: expected ({len(SPECTRA_ROWS)}, {n}, nk) with the rows' nk")
+        if self.ncs == 0:
+            self.cs_kx, self.cs_kz = np.zeros_like(ckx), np.zeros_like(ckz)
+            self.cs_ekx, self.cs_ekz = np.zeros_like(ekx), np.zeros_like(ekz)
+            self.cs_refs, self.cs_rows = refs, rows
+            self.cs_k = (np.asarray(kx, float).copy(), np.asarray(kz, float).copy())
+            self.cs_nxz = (int(nx) if nx else 2 * (ckx.shape[3] - 1), int(nz) if nz else 2 * (ckz.shape[3] - 1))
+        elif refs != self.cs_refs or rows != self.cs_rows or ckx.shape != self.cs_kx.shape or ckz.shape != self.cs_kz.shape:
+            raise ValueError("cross-spectra of other reference planes, rows or sizes than the first sample's")
+        self.cs_kx += ckx
+        self.cs_kz += ckz
+        self.cs_ekx += ekx
+        self.cs_ekz += ekz
+        self.ncs += 1
+
+    def cross_correlations(self) -> dict:
+        """Two-point correlations across planes from the averaged cross-spectra.  Three-dimensional, so
+        kept out of ``profiles``:
+
+          ref_planes, ref_y_plus         [nref']         the reference planes after folding and their wall distance
+          y_plus                         [NY]            of every plane, from the reference plane's wall
+          r_x_plus, r_z_plus             [NX], [NZp]     the signed separations -n/2 .. n/2 - 1 grid intervals
+          R_x[row], R_z[row]             [nref', NY, n]  <a'(x + r, y) b'(x, y_r)> / sqrt(<a'a'>(y) <b'b'>(y_r))
+          R_y[row]                       [nref', NY]     the same at zero separation
+          coherence_kx[row], coherence_kz[row]  [nref', NY, nk]  |C|^2 / (E_a(y) E_b(y_r)) per wavenumber bin
+
+        all 0 where the denominator is 0 (the walls).  A reference plane j and its mirror NY - 1 - j are
+        folded when both were sampled, a single one stands alone, as in ``pdfs``.  The upper one is
+        reflected (y -> NY - 1 - y); v, omega_x and omega_z are odd under the reflection, so the rows uv,
+        u_wz and w_wx change sign.  The variances and spectra of the denominators are folded alike."""
+        if self.ncs == 0 or self.n == 0:
+            raise ValueError("no cross-spectra samples")
+        from ..reference.cross_spectra import ODD_ROWS, ROW_FACTORS, cross_correlations
+
+        n = self.y.size
+        ut, nu = self.utau(), self.nu
+        pos = {j: i for i, j in enumerate(self.cs_refs)}
+        refs = sorted({min(j, n - 1 - j) for j in self.cs_refs})
+        srow = {name: q for q, name in enumerate(SPECTRA_ROWS)}
+        out = {"ref_planes": np.array(refs), "ref_y_plus": (1.0 + self.y[refs]) * ut / nu, "y_plus": (1.0 + self.y) * ut / nu,
+               "R_x": {}, "R_z": {}, "R_y": {}, "coherence_kx": {}, "coherence_kz": {}}
+
+        def ratio(a, d):
+            ok = d > 0
+            return np.where(ok, a / np.where(ok, d, 1.0), 0.0)
+
+        for d, k, c, e, nn in (("x", self.cs_k[0], self.cs_kx / self.ncs, self.cs_ekx / self.ncs, self.cs_nxz[0]),
+                               ("z", self.cs_k[1], self.cs_kz / self.ncs, self.cs_ekz / self.ncs, self.cs_nxz[1])):
+            out[f"r_{d}_plus"] = (np.arange(nn) - nn // 2) * (2.0 * np.pi / k[1] / nn if k.size > 1 else 0.0) * ut / nu
+            for q, row in enumerate(self.cs_rows):
+                ea, eb = e[srow[ROW_FACTORS[row][0]]], e[srow[ROW_FACTORS[row][1]]]
+                C = np.zeros((len(refs),) + c.shape[2:], complex)
+                Ea = np.zeros((len(refs),) + ea.shape)
+                Eb = np.zeros((len(refs), eb.shape[1]))
+                for r, j in enumerate(refs):
+                    parts = 0
+                    if j in pos:
+                        C[r] += c[q, pos[j]]
+                        Ea[r] += ea
+                        Eb[r] += eb[j]
+                        parts += 1
+                    if n - 1 - j != j and n - 1 - j in pos:
+                        C[r] += (-1.0 if row in ODD_ROWS else 1.0) * c[q, pos[n - 1 - j]][::-1]
+                        Ea[r] += ea[::-1]
+                        Eb[r] += eb[n - 1 - j]
+                        parts += 1
+                    C[r] /= parts
+                    Ea[r] /= parts
+                    Eb[r] /= parts
+                norm = np.sqrt(Ea.sum(-1) * Eb.sum(-1)[:, None])              # [nref', NY]
+                out[f"R_{d}"][row] = ratio(cross_correlations(C, nn), norm[:, :, None])
+                out[f"coherence_k{d}"][row] = ratio(np.abs(C) ** 2, Ea * Eb[:, None, :])
+                if d == "x":
+                    out["R_y"][row] = ratio(C.real.sum(-1), norm)
         return out
 
     def add_pressure_strain(self, ps):

@@ -101,6 +101,7 @@ PYBIND11_MODULE(_core, m) {
       RW(max_rollbacks) RW(rollback_cfl_factor) RW(spectra_every) RW(spectra_planes) RW(log_json)
       RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every)
       RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure) RW(sbudget_every)
+      RW(ycross_every) RW(ycross_planes) RW(ycross_rows)
       RW(pdf_every) RW(pdf_planes) RW(pdf_bins) RW(pdf_joint_bins) RW(pdf_span) RW(pdf_vorticity);
 #undef RW
 
@@ -381,6 +382,35 @@ PYBIND11_MODULE(_core, m) {
            "1-D spectra and co-spectra uu, vv, ww, uv, wxwx, wywy, wzwz, pp of the current state at every plane: ekx "
            "(8, NY, Kx+1) by |kx|, ekz (8, NY, nkz) by kz, global over the communicator; row pp is zero unless "
            "pressure (one rank)")
+      .def("plane_cross_spectra",
+           [](Solver& s, const std::vector<int>& refs, const std::string& rows) {
+             // the arrays view the result in place (a capsule owns it): no second host copy
+             auto cs = std::make_unique<Solver::PlaneCrossSpectra>();
+             {
+               py::gil_scoped_release r;
+               *cs = s.plane_cross_spectra(refs, rows);
+             }
+             Solver::PlaneCrossSpectra* raw = cs.release();
+             py::capsule owner(raw, [](void* q) { delete static_cast<Solver::PlaneCrossSpectra*>(q); });
+             const Plan& p = s.plan();
+             auto arr = [&](const std::complex<double>* v, int nk) {
+               return py::array_t<std::complex<double>>({static_cast<py::ssize_t>(4), static_cast<py::ssize_t>(raw->ref_planes.size()),
+                                                         static_cast<py::ssize_t>(p.NY), static_cast<py::ssize_t>(nk)}, v, owner);
+             };
+             py::dict d;
+             d["rows"] = raw->rows;
+             d["ref_planes"] = raw->ref_planes;
+             d["ckx"] = arr(raw->kx(), p.Kx + 1);
+             d["ckz"] = arr(raw->kz(), p.nkz);
+             return d;
+           },
+           py::arg("ref_planes"), py::arg("rows") = "velocity",
+           "cross-spectra of every plane against the reference planes (distinct, at most 16), rows uu vv ww uv (velocity) or "
+           "u_wz v_wz w_wx wz_wz (shear), the first factor at y and the conjugated second at the reference plane: ckx "
+           "(4, nref, NY, Kx+1) by |kx|, ckz (4, nref, NY, nkz) by kz, complex, global over the communicator")
+      .def("plane_cross_spectra_timing", &Solver::plane_cross_spectra_timing, py::call_guard<py::gil_scoped_release>(),
+           py::arg("ref_planes"), py::arg("rows") = "velocity",
+           "device ms of the launches of one plane_cross_spectra() and of one plane_spectra(): [ycross, yspectra]")
       .def("spectral_budgets",
            [](Solver& s) {
              // the arrays view the result in place (a capsule owns it): no second host copy

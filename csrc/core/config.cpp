@@ -232,6 +232,9 @@ Config Config::from_tree(const ConfigTree& t) {
   c.yspectra_every = static_cast<int>(t.get_int(pick(t, "yspectra_every"), c.yspectra_every));
   c.yspectra_pressure = static_cast<int>(t.get_int(pick(t, "yspectra_pressure"), c.yspectra_pressure));
   c.sbudget_every = static_cast<int>(t.get_int(pick(t, "sbudget_every"), c.sbudget_every));
+  c.ycross_every = static_cast<int>(t.get_int(pick(t, "ycross_every"), c.ycross_every));
+  c.ycross_planes = t.get_string(pick(t, "ycross_planes"), c.ycross_planes);
+  c.ycross_rows = t.get_string(pick(t, "ycross_rows"), c.ycross_rows);
   c.pdf_every = static_cast<int>(t.get_int(pick(t, "pdf_every"), c.pdf_every));
   c.pdf_planes = t.get_string(pick(t, "pdf_planes"), c.pdf_planes);
   c.pdf_bins = static_cast<int>(t.get_int(pick(t, "pdf_bins"), c.pdf_bins));
@@ -302,6 +305,8 @@ std::vector<int> Config::pdf_plane_list() const {
   return out;
 }
 
+std::vector<int> Config::ycross_plane_list() const { return int_list(ycross_planes, "ycross_planes"); }
+
 int phys_field_index(const std::string& name) {
   static const char* kNames[6] = {"u", "v", "w", "wx", "wy", "wz"};
   for (int f = 0; f < 6; ++f)
@@ -343,7 +348,7 @@ void Config::validate() const {
   CH_CHECK(stats_every >= 0 && symmetry_every >= 0 && checkpoint_every >= 0 && log_every >= 0 &&
                spectra_every >= 0 && snapshot_every >= 0 && health_every >= 1 && fields_every >= 0 && moments_every >= 0 &&
                budget_every >= 0 && pressure_every >= 0 && pstrain_every >= 0 && yspectra_every >= 0 && pdf_every >= 0 &&
-               sbudget_every >= 0,
+               sbudget_every >= 0 && ycross_every >= 0,
            "cadences must be >= 0 (health_every >= 1)");
   CH_CHECK(yspectra_pressure == 0 || yspectra_pressure == 1, "yspectra_pressure must be 0|1");
   CH_CHECK(on_nan == "abort" || on_nan == "rollback", "on_nan must be abort|rollback");
@@ -358,6 +363,16 @@ void Config::validate() const {
     CH_CHECK(phys_field_index(f) >= 0, "fields: unknown field '" << f << "' (u, v, w, wx, wy, wz, p)");
   for (int j : pdf_plane_list())
     CH_CHECK(j >= 0 && j < NY, "pdf_planes: y index " << j << " outside [0, NY)");
+  {
+    const std::vector<int> refs = ycross_plane_list();
+    CH_CHECK(ycross_every == 0 || !refs.empty(), "ycross_planes: at least one reference plane is required with ycross_every");
+    CH_CHECK(refs.size() <= 16, "ycross_planes: at most 16 reference planes");
+    for (size_t i = 0; i < refs.size(); ++i) {
+      CH_CHECK(refs[i] >= 0 && refs[i] < NY, "ycross_planes: y index " << refs[i] << " outside [0, NY)");
+      for (size_t k = 0; k < i; ++k) CH_CHECK(refs[k] != refs[i], "ycross_planes: y index " << refs[i] << " given twice");
+    }
+  }
+  CH_CHECK(ycross_rows == "velocity" || ycross_rows == "shear", "ycross_rows must be velocity|shear");
   CH_CHECK(pdf_bins >= 2 && pdf_bins % 2 == 0 && pdf_bins <= 256, "pdf_bins must be even, in [2, 256]");
   CH_CHECK(pdf_joint_bins >= 1 && pdf_joint_bins <= 64 && pdf_bins % pdf_joint_bins == 0,
            "pdf_joint_bins must divide pdf_bins and be at most 64");
@@ -396,6 +411,8 @@ std::string Config::to_string() const {
   o << "  pstrain_every = " << pstrain_every << ";\n";
   o << "  yspectra_every = " << yspectra_every << ";\n  yspectra_pressure = " << yspectra_pressure << ";\n";
   o << "  sbudget_every = " << sbudget_every << ";\n";
+  o << "  ycross_every = " << ycross_every << ";\n  ycross_planes = \"" << ycross_planes << "\";\n";
+  o << "  ycross_rows = \"" << ycross_rows << "\";\n";
   o << "  pdf_every = " << pdf_every << ";\n  pdf_planes = \"" << pdf_planes << "\";\n";
   o << "  pdf_bins = " << pdf_bins << ";\n  pdf_joint_bins = " << pdf_joint_bins << ";\n";
   o << "  pdf_span = " << pdf_span << ";\n  pdf_vorticity = " << pdf_vorticity << ";\n";

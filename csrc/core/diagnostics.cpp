@@ -5,12 +5,14 @@
 // everything here goes on the compute stream behind whatever is queued and writes nothing the next
 // step reads, so the step graphs stay valid.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <functional>
 #include <string>
+#include <thread>
 
 #include "channel/common.hpp"
 #include "channel/solver.hpp"
@@ -869,7 +871,7 @@ std::vector<double> Solver::gradient_sums() {
 
 // With the pressure row the device part of static_pressure_hat() runs first (it writes d_pres_ and the
 // step's scratch).
-Solver::PlaneSpectra Solver::plane_spectra(bool pressure) {
+Solver::PlaneSpectra Solver::plane_spectra(bool pressure, double* ms) {
   CH_CHECK(!pressure || !comm_, "plane_spectra: the pressure row is single-rank (a solver without a communicator)");
   const Plan& p = plan_;
   const size_t nx = static_cast<size_t>(kYSpecRows) * p.NY * (p.Kx + 1), nz = static_cast<size_t>(kYSpecRows) * p.NY * p.nkz;
@@ -883,7 +885,20 @@ Solver::PlaneSpectra Solver::plane_spectra(bool pressure) {
   a.nkz = p.nkz;
   a.ekx = d_yspec_;
   a.ekz = d_yspec_ + nx;
+  hipEvent_t te[2] = {nullptr, nullptr};
+  if (ms) {
+    for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(te[0], s_comp_));
+  }
   for_kblocks([&](size_t off, int cnt, int kx0) { yspectra_accumulate(at_block(a, off, cnt, kx0), fp64_, s_comp_); });
+  if (ms) {
+    float t = 0;
+    HIP_CHECK(hipEventRecord(te[1], s_comp_));
+    HIP_CHECK(hipEventSynchronize(te[1]));
+    HIP_CHECK(hipEventElapsedTime(&t, te[0], te[1]));
+    *ms = t;
+    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+  }
   PlaneSpectra out;
   out.rows = {"uu", "vv", "ww", "uv", "wxwx", "wywy", "wzwz", "pp"};
   // (through pinned memory: a copy into fresh pageable vectors runs at a fraction of the link's rate)
@@ -914,6 +929,128 @@ void Solver::write_yspectra_files() {
   js << "{\"step\": " << nstep_ << ", \"time\": " << time() << ", \"rows\": [";
   for (size_t k = 0; k < sp.rows.size(); ++k) js << (k ? ", " : "") << "\"" << sp.rows[k] << "\"";
   js << "], \"pressure\": " << (pres ? "true" : "false") << ", \"ax\": " << p.ax << ", \"az\": " << p.az << ", \"y\": [";
+  for (int j = 0; j < p.NY; ++j) js << (j ? ", " : "") << grid_.y[j];
+  js << "], \"Re\": " << cfg_.Re << "}\n";
+}
+
+// ---- cross-spectra against reference planes ------------------------------------------------------
+// One launch set per kx sub-block with the reference planes as a grid factor, one all-reduce, one copy
+// through pinned memory; the sums are sized by the reference planes of the call (17 MB each at the
+// headline grid) and kept for the next one.  Reads the fields and writes its own sums only.
+Solver::PlaneCrossSpectra Solver::plane_cross_spectra(const std::vector<int>& refs, const std::string& rows, double* ms) {
+  const Plan& p = plan_;
+  CH_CHECK(rows == "velocity" || rows == "shear", "plane_cross_spectra: unknown row set '" << rows << "' (velocity, shear)");
+  CH_CHECK(!refs.empty(), "plane_cross_spectra: no reference plane");
+  CH_CHECK(static_cast<int>(refs.size()) <= kYCrossMaxRefs, "plane_cross_spectra: more than " << kYCrossMaxRefs << " reference planes");
+  for (size_t i = 0; i < refs.size(); ++i) {
+    CH_CHECK(refs[i] >= 0 && refs[i] < p.NY, "plane_cross_spectra: reference plane " << refs[i] << " outside [0, NY)");
+    for (size_t k = 0; k < i; ++k) CH_CHECK(refs[k] != refs[i], "plane_cross_spectra: reference plane " << refs[i] << " given twice");
+  }
+  const size_t nref = refs.size(), NY = static_cast<size_t>(p.NY), nkx = static_cast<size_t>(p.Kx) + 1, nkz = static_cast<size_t>(p.nkz);
+  const size_t nx = nref * kYSpecRows * NY * nkx, nz = nref * kYSpecRows * NY * nkz;
+  if (ycross_n_ < nx + nz) {
+    wait(s_comp_);
+    if (d_ycross_) HIP_CHECK(hipFree(d_ycross_));
+    if (h_ycross_) HIP_CHECK(hipHostFree(h_ycross_));
+    d_ycross_ = h_ycross_ = nullptr;
+    ycross_n_ = 0;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_ycross_), (nx + nz) * sizeof(double)));
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_ycross_), (nx + nz) * sizeof(double), hipHostMallocDefault));
+    ycross_n_ = nx + nz;
+  }
+  if (!prepared_) prepare();
+  hipEvent_t te[2] = {nullptr, nullptr};
+  if (ms)
+    for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
+  HIP_CHECK(hipMemsetAsync(d_ycross_, 0, (nx + nz) * sizeof(double), s_comp_));
+  const bool shear = rows == "shear";
+  YCrossArgs a;
+  walk_args(a, shear ? (1u | 2u | 4u | 8u | 32u) : (1u | 2u | 4u), false);
+  a.nkz = p.nkz;
+  a.rows = shear ? kYCrossShear : kYCrossVelocity;
+  a.nref = static_cast<int>(nref);
+  for (size_t i = 0; i < nref; ++i) a.yref[i] = refs[i];
+  a.ckx = d_ycross_;
+  a.ckz = d_ycross_ + nx;
+  if (ms) HIP_CHECK(hipEventRecord(te[0], s_comp_));
+  for_kblocks([&](size_t off, int cnt, int kx0) { ycross_accumulate(at_block(a, off, cnt, kx0), fp64_, s_comp_); });
+  if (ms) HIP_CHECK(hipEventRecord(te[1], s_comp_));
+  reduce_fetch(d_ycross_, nx + nz, h_ycross_);
+  if (ms) {
+    float t = 0;
+    HIP_CHECK(hipEventElapsedTime(&t, te[0], te[1]));
+    *ms = t;
+    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+  }
+  PlaneCrossSpectra out;
+  out.rows = shear ? std::vector<std::string>{"u_wz", "v_wz", "w_wx", "wz_wz"} : std::vector<std::string>{"uu", "vv", "ww", "uv"};
+  out.ref_planes = refs;
+  out.nkx = nkx;
+  out.nkz = nkz;
+  out.ckx.reset(new double[2 * 4 * nref * NY * nkx]);
+  out.ckz.reset(new double[2 * 4 * nref * NY * nkz]);
+  // device rows [ref][2 q + (Re, Im)][y][k] -> complex [q][ref][y][k]: one (array, row, reference plane)
+  // block per task, on a few threads (the pages of the result are touched here for the first time)
+  const size_t tasks = 2 * 4 * nref;
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t t = next++; t < tasks; t = next++) {
+      const bool z = t >= 4 * nref;
+      const size_t q = (z ? t - 4 * nref : t) / nref, r = (z ? t - 4 * nref : t) % nref;
+      const size_t plane = NY * (z ? nkz : nkx);
+      const double* re = h_ycross_ + (z ? nx : 0) + (r * kYSpecRows + 2 * q) * plane;
+      const double* im = re + plane;
+      double* o = (z ? out.ckz.get() : out.ckx.get()) + 2 * (q * nref + r) * plane;
+      for (size_t e = 0; e < plane; ++e) {
+        o[2 * e] = re[e];
+        o[2 * e + 1] = im[e];
+      }
+    }
+  };
+  std::vector<std::thread> pool;
+  for (size_t t = 1; t < std::min<size_t>(8, tasks); ++t) pool.emplace_back(work);
+  work();
+  for (std::thread& t : pool) t.join();
+  return out;
+}
+
+std::vector<double> Solver::plane_cross_spectra_timing(const std::vector<int>& refs, const std::string& rows) {
+  std::vector<double> ms(2, 0.0);
+  plane_cross_spectra(refs, rows, &ms[0]);
+  plane_spectra(false, &ms[1]);
+  return ms;
+}
+
+// <path>YCROSS_KX_<step>.npy (4, nref, NY, Kx+1) and <path>YCROSS_KZ_<step>.npy (4, nref, NY, nkz), complex128,
+// and a sidecar <path>YCROSS_<step>.json; every rank takes part in the sums, rank 0 writes
+void Solver::write_ycross_files() {
+  const PlaneCrossSpectra cs = plane_cross_spectra(cfg_.ycross_plane_list(), cfg_.ycross_rows);
+  if (plan_.rank != 0) return;
+  const Plan& p = plan_;
+  char step[16];
+  std::snprintf(step, sizeof(step), "%08ld", nstep_);
+  const size_t nref = cs.ref_planes.size();
+  auto write = [&](const char* name, const double* v, int nk) {
+    const std::string fn = cfg_.path + name + step + ".npy";
+    std::ofstream f(fn, std::ios::binary | std::ios::trunc);
+    CH_CHECK(f.good(), "cannot open '" << fn << "'");
+    const std::string h = npy_header("<c16", "(4, " + std::to_string(nref) + ", " + std::to_string(p.NY) + ", " + std::to_string(nk) + ")");
+    f.write(h.data(), static_cast<std::streamsize>(h.size()));
+    f.write(reinterpret_cast<const char*>(v), static_cast<std::streamsize>(2 * 4 * nref * p.NY * static_cast<size_t>(nk) * sizeof(double)));
+    f.close();
+    CH_CHECK(!f.fail(), "writing '" << fn << "' failed");
+  };
+  write("YCROSS_KX_", cs.ckx.get(), p.Kx + 1);
+  write("YCROSS_KZ_", cs.ckz.get(), p.nkz);
+  std::ofstream js(cfg_.path + "YCROSS_" + step + ".json");
+  js.precision(17);
+  js << "{\"step\": " << nstep_ << ", \"time\": " << time() << ", \"rows\": [";
+  for (size_t k = 0; k < cs.rows.size(); ++k) js << (k ? ", " : "") << "\"" << cs.rows[k] << "\"";
+  js << "], \"row_set\": \"" << cfg_.ycross_rows << "\", \"ref_planes\": [";
+  for (size_t k = 0; k < nref; ++k) js << (k ? ", " : "") << cs.ref_planes[k];
+  js << "], \"ref_y\": [";
+  for (size_t k = 0; k < nref; ++k) js << (k ? ", " : "") << grid_.y[cs.ref_planes[k]];
+  js << "], \"ax\": " << p.ax << ", \"az\": " << p.az << ", \"y\": [";
   for (int j = 0; j < p.NY; ++j) js << (j ? ", " : "") << grid_.y[j];
   js << "], \"Re\": " << cfg_.Re << "}\n";
 }

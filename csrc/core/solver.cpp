@@ -461,11 +461,15 @@ void Solver::free_all() {
   for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
                   static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
                   static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_),
-                  static_cast<void*>(d_yspec_), d_hist_, static_cast<void*>(d_sbud_)})
+                  static_cast<void*>(d_yspec_), d_hist_, static_cast<void*>(d_sbud_), static_cast<void*>(d_ycross_)})
     if (p) (void)hipFree(p);
   d_pstr_ = nullptr;
   d_yspec_ = nullptr;
   d_sbud_ = nullptr;
+  d_ycross_ = nullptr;
+  ycross_n_ = 0;
+  if (h_ycross_) (void)hipHostFree(h_ycross_);
+  h_ycross_ = nullptr;
   if (h_sbud_) (void)hipHostFree(h_sbud_);
   h_sbud_ = nullptr;
   d_hist_ = nullptr;
@@ -2192,6 +2196,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (cfg_.pstrain_every > 0 && nstep_ % cfg_.pstrain_every == 0) write_pstrain_files();
     if (cfg_.yspectra_every > 0 && nstep_ % cfg_.yspectra_every == 0) write_yspectra_files();
     if (cfg_.sbudget_every > 0 && nstep_ % cfg_.sbudget_every == 0) write_sbudget_files();
+    if (cfg_.ycross_every > 0 && nstep_ % cfg_.ycross_every == 0) write_ycross_files();
     if (cfg_.pdf_every > 0 && nstep_ % cfg_.pdf_every == 0) write_pdf_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();

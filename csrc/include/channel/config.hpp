@@ -96,6 +96,9 @@ struct Config {
   int yspectra_every = 0;              // 0 = off; 1-D spectra and co-spectra at every plane (YSPEC_KX_<step>.npy, YSPEC_KZ_<step>.npy, YSPEC_<step>.json; any P)
   int sbudget_every = 0;               // 0 = off; spectral Reynolds-stress budgets at every plane (SBUD_KX_<step>.npy, SBUD_KZ_<step>.npy, SBUD_<step>.json; one rank)
   int yspectra_pressure = 0;           // 1 = also the pressure row of those spectra (one rank)
+  int ycross_every = 0;                // 0 = off; cross-spectra of every plane against ycross_planes (YCROSS_KX_<step>.npy, YCROSS_KZ_<step>.npy, YCROSS_<step>.json; any P)
+  std::string ycross_planes = "";      // comma-separated reference y indices (distinct, at most 16; required when on)
+  std::string ycross_rows = "velocity";  // velocity (uu, vv, ww, uv) | shear (u_wz, v_wz, w_wx, wz_wz)
   int pdf_every = 0;                   // 0 = off; histograms, joint (u, v) histogram and quadrant sums (PDF_<step>.npy, JPDF_UV_<step>.npy, QUAD_<step>.npy, PDF_<step>.json; one rank)
   std::string pdf_planes = "";         // comma-separated y indices ("" = every plane)
   int pdf_bins = 128;                  // bins per 1-D histogram (even, at most 256)
@@ -114,6 +117,7 @@ struct Config {
   std::vector<int> fields_plane_list() const;    // parsed fields_planes (default: 0 .. NY-1)
   std::vector<std::string> fields_list() const;  // parsed fields
   std::vector<int> pdf_plane_list() const;       // parsed pdf_planes (default: 0 .. NY-1)
+  std::vector<int> ycross_plane_list() const;    // parsed ycross_planes, in the order given
 };
 
 // FFT lengths the transform kernels are instantiated for: 2^k (16..2048) and 3, 5, 7, 9, 11, 13, 15 x 2^k

@@ -464,6 +464,27 @@ struct SBudgetArgs : SpecWalkArgs {
   double* ekz = nullptr;              // [kSBudRows][N][nkz]
 };
 void sbudget_accumulate(const SBudgetArgs& a, bool fp64, hipStream_t s);
+// Cross-spectra of every plane against a few reference planes: with e = a(kx, kz, y) conj(b(kx, kz, y_r))
+// of every stored element (walk, weights and masks of the spectra above: kz = 0 once, kz > 0 twice, the
+// mean line and the padded lines skipped; products and sums in double), per reference plane r and plane y
+//   ckx[|kx|] += wgt (kx > 0 ? e : kx < 0 ? conj(e) : Re e)      (summed over kz)
+//   ckz[kz]   += wgt e                                             (summed over kx)
+// so that <a'(x + r_x, y, z) b'(x, y_r, z)> = Re sum_k ckx[k] exp(i k ax r_x), and likewise in z with ckz.
+// The kYSpecRows real rows are (Re, Im) of the four complex rows of the row set:
+//   kYCrossVelocity  u u*, v v*, w w*, u v*
+//   kYCrossShear     u omega_z*, v omega_z*, w omega_x*, omega_z omega_z*      (a at y, b at y_r)
+// A reference plane is read from the same kx sub-block as the planes it is paired with.
+constexpr int kYCrossMaxRefs = 16;
+enum { kYCrossVelocity = 0, kYCrossShear = 1 };
+struct YCrossArgs : SpecWalkArgs {    // u, v, w; the shear set also omega_x and omega_z
+  int nkz = 0;                        // global retained kz count
+  int rows = kYCrossVelocity;
+  int nref = 0;
+  int yref[kYCrossMaxRefs] = {};      // distinct planes in [0, N)
+  double* ckx = nullptr;              // [nref][kYSpecRows][N][Kx + 1]
+  double* ckz = nullptr;              // [nref][kYSpecRows][N][nkz]
+};
+void ycross_accumulate(const YCrossArgs& a, bool fp64, hipStream_t s);
 // element (local kx 0, kz 0) of every plane y < N of one spectral field (lines = nkx_loc * nkzs) := 0
 void zero_mean_line(void* q, int N, int kzb, int lines, bool fp64, hipStream_t s);
 // fault injection (tests): element `elem` of a complex field becomes NaN

@@ -185,7 +185,25 @@ class Solver {
     std::vector<std::string> rows;
     std::vector<double> ekx, ekz;
   };
-  PlaneSpectra plane_spectra(bool pressure = false);
+  PlaneSpectra plane_spectra(bool pressure = false, double* ms = nullptr);  // ms: the device time of the launches
+  // Cross-spectra of every plane against the reference planes refs (distinct, in [0, NY), at most
+  // kYCrossMaxRefs; kernels.hpp YCrossArgs): ckx [4][nref][NY][Kx+1] by |kx| and ckz [4][nref][NY][nkz] by
+  // kz, complex, of the row set "velocity" (uu, vv, ww, uv) or "shear" (u_wz, v_wz, w_wx, wz_wz), the first
+  // factor at y and the conjugated second at the reference plane.  Global (any communicator; all-reduced
+  // like plane_spectra()).  ms: the device time of the launches.
+  struct PlaneCrossSpectra {
+    std::vector<std::string> rows;
+    std::vector<int> ref_planes;
+    // (Re, Im) pairs, 2 * 4 * nref * NY * nk doubles each; not value-initialised: at 16 planes and the
+    // headline grid the result is 270 MB, and its first touch is spread over the threads that fill it
+    std::unique_ptr<double[]> ckx, ckz;
+    size_t nkx = 0, nkz = 0;             // bins per (row, reference plane, plane): Kx + 1, nkz
+    const std::complex<double>* kx() const { return reinterpret_cast<const std::complex<double>*>(ckx.get()); }
+    const std::complex<double>* kz() const { return reinterpret_cast<const std::complex<double>*>(ckz.get()); }
+  };
+  PlaneCrossSpectra plane_cross_spectra(const std::vector<int>& refs, const std::string& rows = "velocity", double* ms = nullptr);
+  // device time in ms of the launches of one plane_cross_spectra() and of one plane_spectra() (tools/export_cost.py)
+  std::vector<double> plane_cross_spectra_timing(const std::vector<int>& refs, const std::string& rows = "velocity");
   // Spectral Reynolds-stress budgets of the current state at every plane (kernels.hpp SBudgetArgs): ekx
   // [kSBudRows][NY][Kx+1] by |kx| and ekz [kSBudRows][NY][nkz] by kz, with the conventions of
   // plane_spectra(); U and dU are the mean profile and its compact first derivative as the rows used
@@ -283,6 +301,7 @@ class Solver {
   void write_pdf_files();
   void write_yspectra_files();
   void write_sbudget_files();
+  void write_ycross_files();
   // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat): the
   // pressure solve, then the return trip of r through physical space (static_return_device)
   void static_pressure_device();
@@ -476,6 +495,9 @@ class Solver {
   bool yspec_note_ = false;   // the "pressure row skipped" note has been printed
   double* d_sbud_ = nullptr;  // spectral budgets: ekx [kSBudRows][NY][Kx+1], ekz [kSBudRows][NY][nkz], then U and dU [NY]
   double* h_sbud_ = nullptr;  // pinned host copy of the sums of d_sbud_
+  double* d_ycross_ = nullptr;  // cross-spectra: ckx [nref][kYSpecRows][NY][Kx+1], then ckz [nref][kYSpecRows][NY][nkz]
+  double* h_ycross_ = nullptr;  // pinned host copy of d_ycross_
+  size_t ycross_n_ = 0;         // doubles both hold (grown to the largest nref asked for)
   bool sbud_note_ = false;    // the "spectral budget files skipped" note has been printed
   double comm_timeout_s_ = 900.0;     // CHANNEL_COMM_TIMEOUT_S (0 = wait forever)
 

@@ -2,7 +2,8 @@
 device part of pressure_hat()), one pressure_moments(), one pressure_strain(), one plane_spectra() without and with
 the pressure row, one spectral_budgets() and one three-field all-plane physical_fields() at 1024x385x1024 fp32, relative to one RK3 step in the same process.
 --skip-fields leaves the (2 s, 10 GB of host memory) all-plane field export out; --pdfs-only stops after the
-histograms; --sbudget-only runs the step, plane_spectra() and spectral_budgets() only."""
+histograms; --sbudget-only runs the step, plane_spectra() and spectral_budgets() only; --ycross-only runs the
+step, plane_spectra() and plane_cross_spectra() for 1, 4 and 16 reference planes only."""
 import json
 import os
 import sys
@@ -60,6 +61,49 @@ def spectral_budget_cost():
     res["sbudget_ps_uu_sum_vs_pstrain"] = float(abs(r["ekz"][14].sum(axis=-1) - ps[0]).max() / abs(ps[0]).max())
 
 
+def cross_spectra_cost():
+    """plane_cross_spectra() for 1, 4 and 16 reference planes of either row set: host time of the whole
+    call, and the device time of its launches by events next to that of plane_spectra()'s in the same
+    process, against the bytes they read (velocity: u, v, w, or the five fields of the combine mode; shear:
+    also omega_z; the reference planes stay in cache)."""
+    nkx, nkz = 2 * (cfg.NX // 3) + 1, (2 * cfg.NZ - 2) // 3 + 1
+    nkzs = (nkz + 7) // 8 * 8 if s.spec_kzb() else nkz
+    field = cfg.NY * nkx * nkzs * 8
+    res["plane_spectra_bytes"] = (5 if s.combine() else 6) * field
+    res["ycross_result_bytes_per_plane"] = 8 * cfg.NY * (cfg.NX // 3 + 1 + nkz) * 8
+    ts = []
+    for rep in range(5):
+        t0 = time.perf_counter()
+        sp = s.plane_spectra()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res["plane_spectra_ms"] = ts
+    sets = {1: [40], 4: [0, 12, 40, 192], 16: [0, 4, 8, 12, 20, 40, 80, 120, 160, 192, 224, 264, 304, 344, 372, 384]}
+    for rows, nf in (("velocity", 3), ("shear", 4)):
+        res[f"ycross_{rows}_bytes_per_plane"] = (5 if s.combine() else nf) * field
+        for n, refs in sets.items():
+            ts = []
+            for rep in range(5):
+                t0 = time.perf_counter()
+                cs = s.plane_cross_spectra(refs, rows)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            tt = [s.plane_cross_spectra_timing(refs, rows) for _ in range(5)]
+            key = f"ycross_{rows}_{n}"
+            res[key + "_ms"] = ts
+            res[key + "_over_step"] = min(ts) / step_ms
+            res[key + "_kernel_ms"] = [t[0] for t in tt]
+            res[key + "_kernel_ms_per_plane"] = min(t[0] for t in tt) / n
+            res[key + "_yspectra_kernel_ms"] = [t[1] for t in tt]
+            res[key + "_kernel_per_plane_over_yspectra"] = res[key + "_kernel_ms_per_plane"] / min(t[1] for t in tt)
+            res[key + "_TBps"] = n * res[f"ycross_{rows}_bytes_per_plane"] / (min(t[0] for t in tt) * 1e-3) / 1e12
+        if rows == "velocity":  # consistency: y = y_r against plane_spectra()
+            own = cs["ckx"][0][9, 192].real
+            res["ycross_uu_own_plane_vs_plane_spectra"] = float(abs(own - sp["ekx"][0][192]).max() / abs(sp["ekx"][0]).max())
+
+
+if "--ycross-only" in sys.argv:
+    cross_spectra_cost()
+    print(json.dumps(res))
+    sys.exit(0)
 if "--sbudget-only" in sys.argv:
     spectral_budget_cost()
     print(json.dumps(res))
