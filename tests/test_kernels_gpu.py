@@ -216,11 +216,20 @@ def _combine_ref(s, NX, Kx, ax, az, kz0):
     (768, 50, torch.complex128, 0, "<768, double, false, 0, 0, 1, 1, true>"),
 ])
 def test_xfft_combine_blocked(native, NX, nkz, dtype, nt, variant):
+    _check_xfft_combine_blocked(native, NX, nkz, dtype, nt, variant, 0.5, 2.0)
+
+
+def test_xfft_combine_blocked_box(native):
+    """ax = 0.75, az = 1.6: none of ax, az, their squares, product and inverses equals another or 1, 2, 4
+    (az = 2 above is the binding's default)."""
+    _check_xfft_combine_blocked(native, 512, 86, torch.complex64, 0, "<512, float, false, 1, 0, 2, 2, true>", 0.75, 1.6)
+
+
+def _check_xfft_combine_blocked(native, NX, nkz, dtype, nt, variant, ax, az):
     rng = np.random.default_rng(NX + nkz + 1)
     Kx = NX // 3
     nkx = 2 * Kx + 1
     rows, y0, ny = 13, 3, 6
-    ax, az = 0.5, 2.0
     s = rng.standard_normal((5, rows, nkx, nkz)) + 1j * rng.standard_normal((5, rows, nkx, nkz))
     idx, fstride = _blocked_index(rows, nkx, nkz)
     buf = np.zeros(5 * fstride, complex)
@@ -238,11 +247,23 @@ def test_xfft_combine_blocked(native, NX, nkz, dtype, nt, variant):
                                               (128, 43, 0, torch.complex128), (96, 13, 3, torch.complex64),
                                               (2048, 9, 0, torch.complex128), (384, 20, 0, torch.complex64)])
 def test_xfft_combine(native, NX, nkz, kz0, dtype):
+    _check_xfft_combine(native, NX, nkz, kz0, dtype, 1.0, 2.0)
+
+
+@pytest.mark.parametrize("NX,nkz,kz0,dtype", [(1024, 21, 5, torch.complex64), (96, 13, 3, torch.complex64),
+                                              (128, 43, 0, torch.complex128), (96, 13, 3, torch.complex128)])
+def test_xfft_combine_box(native, NX, nkz, kz0, dtype):
+    """The plain layout (the P > 1 path) away from ax = 1, az = 2, the identity and the binding's defaults,
+    which a dropped factor or an unfilled argument would pass: ax = 0.75, az = 1.6 on the kz0 > 0 cases
+    (a pencil row's kz range, where az (kz0 + kz) must hold) and in fp64."""
+    _check_xfft_combine(native, NX, nkz, kz0, dtype, 0.75, 1.6)
+
+
+def _check_xfft_combine(native, NX, nkz, kz0, dtype, ax, az):
     rng = np.random.default_rng(NX + kz0)
     Kx = NX // 3
     nkx = 2 * Kx + 1
     ny = 5
-    ax, az = 1.0, 2.0
     s = rng.standard_normal((5, ny, nkx, nkz)) + 1j * rng.standard_normal((5, ny, nkx, nkz))
     st = torch.tensor(s, dtype=dtype, device=DEV)
     phys = native.xfft_backward(st, NX, Kx, combine=1, ax=ax, az=az, kz0=kz0)

@@ -20,14 +20,21 @@ pytestmark = pytest.mark.gpu
 GRID = dict(NX=32, NY=33, NZ=17)
 
 
-def _global_state():
+def _global_state(geom=None):
+    """geom: a geometry of geomchecks.py (the same seed and amplitude on its wavenumbers, y grid and
+    flux); None: the default box."""
+    if geom is not None:
+        import geomchecks as gc
+
+        m = gc.MULTIRANK
+        return gc.make_state(*m["grid"], geom, m["seed"], m["amp"])
     plan = ora.OraclePlan(**GRID)
     ops = ora.build_ops(GRID["NY"])
     phi, om = ora.random_state(plan, ops, seed=5, amp=0.3)
     return phi, om, 0.75 * 1.8 * (1 - ops.y ** 2)
 
 
-def _worker(rank, world, shm, outdir, nsteps, pr=1):
+def _worker(rank, world, shm, outdir, nsteps, pr=1, geom=None):
     import torch  # noqa: F401
 
     from channel_gpu_amd import require_native
@@ -35,11 +42,12 @@ def _worker(rank, world, shm, outdir, nsteps, pr=1):
 
     C = require_native()
     cfg = default_config(**GRID, Re=400.0, precision="fp64", dt_fixed=0.01, ic="zero", stats_every=0,
-                         log_every=0, symmetry_every=0, decomposition="pencil" if pr > 1 else "slab", pr=pr)
+                         log_every=0, symmetry_every=0, decomposition="pencil" if pr > 1 else "slab", pr=pr,
+                         **(geom or {}))
     s = C.Solver(cfg, rank, world, 0, shm.encode())
     p = s.plan
     assert p.Pr == pr and p.Pr * p.Pc == world
-    phi, om, U = _global_state()
+    phi, om, U = _global_state(geom)
     sl = slice(p.kx0, p.kx0 + p.nkx_loc)
     sz = slice(p.kz0, p.kz0 + p.nkz_loc)
     s.set_state(np.ascontiguousarray(phi[:, sl, sz]), np.ascontiguousarray(om[:, sl, sz]), U)
@@ -54,7 +62,7 @@ def _worker(rank, world, shm, outdir, nsteps, pr=1):
     s.symmetrize()  # distributed kz=0 column exchange
     sphi, som, _ = s.get_state()
     np.savez(os.path.join(outdir, f"r{rank}.npz"), phi=gphi, om=gom, U=gU, sphi=sphi, som=som, health=s.health(),
-             kx0=p.kx0, kz0=p.kz0)
+             kx0=p.kx0, kz0=p.kz0, combine=s.combine())
     del s
 
 
@@ -84,12 +92,30 @@ def test_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mo
     communicator.  kzb = 1: the blocked spectral layout at P > 1 (CHANNEL_SPEC_KZB=1; the default at
     R = 7, 8): y split in whole 8-plane tiles (NY = 33 over 3: 8 / 16 / 9 rows), exchange blocks
     and segments in tiles, the distributed kz = 0 symmetrisation on blocked fields."""
+    _check_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mode, kzb)
+
+
+@pytest.mark.parametrize("world,pr", [(2, 1), (4, 2)])
+def test_multirank_matches_oracle_geometry(native, monkeypatch, world, pr):
+    """The same run and bounds on geomchecks.GEOM_A (ax = 0.75, az = 1.6, stretch 1.6, Q = 1.3;
+    test_geometry_cpu.py holds the precondition that the oracle's two steps tell it from the default
+    box): the slab, whose x-backward runs the combine mode by default with kx0 > 0 on rank 1, and the
+    2 x 2 pencil with kz0 > 0 on the second process row."""
+    import geomchecks as gc
+
+    parts = _check_multirank_matches_oracle(native, monkeypatch, world, pr, "0", "direct", "0", gc.GEOM_A)
+    assert any(int(q["kx0"]) > 0 for q in parts) and (pr == 1 or any(int(q["kz0"]) > 0 for q in parts))
+    if pr == 1:
+        assert all(bool(q["combine"]) for q in parts)
+
+
+def _check_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mode, kzb, geom=None):
     monkeypatch.setenv("CHANNEL_YCHUNK", chunk)
     monkeypatch.setenv("CHANNEL_A2A_SELF", self_mode)
     monkeypatch.setenv("CHANNEL_SPEC_KZB", kzb)
     nsteps = 2
-    ref = ora.OracleSolver(**GRID, Re=400.0, dt_fixed=0.01)
-    phi, om, U = _global_state()
+    ref = ora.OracleSolver(**GRID, Re=400.0, dt_fixed=0.01, **(geom or {}))
+    phi, om, U = _global_state(geom)
     ref.set_state(phi, om, U)
     for _ in range(nsteps):
         ref.step()
@@ -100,7 +126,7 @@ def test_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mo
         # created the file (the planes of rank 1 would be lost without an error)
         with open(os.path.join(d, "Ga.h5.turn"), "w") as f:
             f.write("1 1\n")
-        mp.start_processes(_worker, args=(world, shm, d, nsteps, pr), nprocs=world, join=True,
+        mp.start_processes(_worker, args=(world, shm, d, nsteps, pr, geom), nprocs=world, join=True,
                            start_method="spawn")
         parts = [dict(np.load(os.path.join(d, f"r{r}.npz"))) for r in range(world)]
         gphi = _assemble(parts, "phi")
@@ -120,7 +146,7 @@ def test_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mo
         if native.hdf5_available():
             from channel_gpu_amd.utils.config import default_config
 
-            cfg = default_config(**GRID, Re=400.0, precision="fp64", ic="zero", stats_every=0, log_every=0)
+            cfg = default_config(**GRID, Re=400.0, precision="fp64", ic="zero", stats_every=0, log_every=0, **(geom or {}))
             s1 = native.Solver(cfg, 0, 1, 0, b"")
             # no UMEAN file named: U from the full-precision 'umean' dataset of the G file
             s1.read_restart(os.path.join(d, "G.h5"), os.path.join(d, "DDV.h5"), "-")
@@ -145,6 +171,7 @@ def test_multirank_matches_oracle(native, monkeypatch, world, pr, chunk, self_mo
             aphi, aom, _ = s2.get_state()
             assert np.array_equal(aphi, rphi) and np.array_equal(aom, rom)
             assert not any(f.endswith(".turn") for f in os.listdir(d))
+    return parts
 
 
 def _worker_adaptive(rank, world, shm, outdir, nsteps, pr=1):

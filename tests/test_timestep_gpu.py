@@ -74,13 +74,15 @@ def test_zphys_cfl_maxima(native, NX, Nzp, dtype):
 
 # ---- 2. dt_update against the formulas ---------------------------------------------------------------
 GEOM = dict(NX=32, NZ=17, LX=2 * math.pi, LZ=math.pi, Re=400.0, NY=33)
+# another box (ax = 0.75, az = 1.6): on the one above NX / (2 pi LX) = NX / (4 pi^2) and LX = 2 LZ
+GEOM_BOX = dict(GEOM, LX=8 * math.pi / 3, LZ=5 * math.pi / 4)
 
 
 def f32(*x):
     return [float(np.float32(v)) for v in x]
 
 
-@pytest.mark.parametrize("name,maxima,kw,bad", [
+DT_CASES = [
     ("corrected", f32(1.3, 0.2, 0.4, 217.3), dict(), False),
     ("zero sum -> dt_max", f32(0.0, 0.0, 0.0, 0.0), dict(), False),
     ("dt_max clamp", f32(1.3, 0.2, 0.4, 3.7), dict(), False),
@@ -91,12 +93,33 @@ def f32(*x):
     ("inf sum", f32(1.3, 0.2, 0.4, math.inf), dict(), True),
     ("nan umax", f32(math.nan, 0.2, 0.4, 217.3), dict(), True),
     ("collapsed dt", f32(1.3, 0.2, 0.4, 1e12), dict(), True),
-])
+]
+
+
+@pytest.mark.parametrize("name,maxima,kw,bad", DT_CASES)
 def test_dt_update_kernel(native, name, maxima, kw, bad):
     """dt_update_kernel against rc.dt_reference (plain Python from COMPAT.md A14): dt_c, dt_v, their
     minimum under dt_max, the dt_fixed override, time advanced by dt, the maxima reset to exactly 0
     and health bit 1 for non-finite maxima or a dt below 1e-12.  fp64 scalar arithmetic: 1e-14."""
-    a = dict(cfl=0.5, dt_max=0.05, dt_fixed=0.0, parity=0, **GEOM)
+    check_dt_update(native, GEOM, name, maxima, kw, bad)
+
+
+@pytest.mark.parametrize("name,maxima,kw,bad", DT_CASES)
+def test_dt_update_kernel_box(native, name, maxima, kw, bad):
+    """The same cases on LX = 8 pi / 3, LZ = 5 pi / 4.  Every case has umax != wmax, so the parity
+    formulas with LX and LZ swapped give another dt_c (and dt_v): by >= 1e-2, against the 1e-14 held."""
+    a = dict(cfl=0.5, dt_max=0.05, dt_fixed=0.0, parity=0, **GEOM_BOX)
+    a.update(kw)
+    if a["parity"]:
+        assert maxima[0] != maxima[2]
+        sw = dict(a, LX=a["LZ"], LZ=a["LX"])
+        for got, want in zip(rc.dt_reference(maxima, **sw)[:2], rc.dt_reference(maxima, **a)[:2]):
+            assert abs(got - want) >= 1e-2 * want, (name, got, want)
+    check_dt_update(native, GEOM_BOX, name, maxima, kw, bad)
+
+
+def check_dt_update(native, geom, name, maxima, kw, bad):
+    a = dict(cfl=0.5, dt_max=0.05, dt_fixed=0.0, parity=0, **geom)
     a.update(kw)
     t0 = 0.734375
     log, health, after = native.dt_update(torch.tensor(maxima, dtype=torch.float32), time0=t0, **a)
