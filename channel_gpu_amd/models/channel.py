@@ -104,8 +104,25 @@ class ChannelFlow:
     def save(self, g: str, ddv: str, umean: str = "-"):
         self.solver.write_restart(g, ddv, umean)
 
-    def load(self, g: str, ddv: str, umean: str = "-"):
-        self.solver.read_restart(g, ddv, umean)
+    def load(self, g: str, ddv: str, umean: str = "-", regrid: bool = False, src_stretch: float | None = None):
+        """Read a restart.  ``regrid`` (or the config key of that name): the files may be on another
+        grid of the same box; modes map by index and every line is interpolated along y on the device
+        (README "Restarting on another grid").  ``src_stretch``: the files' tanh stretching (default:
+        the config's ``regrid_stretch``, else the files' ``stretch`` attribute, else the config's)."""
+        if regrid or self.cfg.regrid:
+            s = self.cfg.regrid_stretch if src_stretch is None else float(src_stretch)
+            self.solver.read_restart_regrid(g, ddv, umean, s)
+        else:
+            self.solver.read_restart(g, ddv, umean)
+        self.solver.prepare()
+
+    def regrid_from(self, phi, omega, U, *, NX: int, NY: int, NZ: int, stretch: float | None = None):
+        """Take a global state on another grid of the same box, in the one-rank ``get_state`` layout
+        ``(NY, nkx, nkz)`` of that grid: the array form of ``load(..., regrid=True)`` (every rank passes
+        the whole source and picks its own lines).  ``stretch``: the source's (default: the config's)."""
+        s = self.cfg.stretch if stretch is None else float(stretch)
+        self.solver.regrid_state(np.asarray(phi, complex), np.asarray(omega, complex), np.asarray(U, float),
+                                 int(NX), int(NY), int(NZ), s)
         self.solver.prepare()
 
     def mean_profile(self) -> np.ndarray:

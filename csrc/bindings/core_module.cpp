@@ -22,6 +22,7 @@
 #include "channel/io.hpp"
 #include "channel/kernels.hpp"
 #include "channel/plan.hpp"
+#include "channel/regrid.hpp"
 #include "channel/solver.hpp"
 
 namespace py = pybind11;
@@ -102,7 +103,8 @@ PYBIND11_MODULE(_core, m) {
       RW(fields_every) RW(fields_planes) RW(fields) RW(moments_every) RW(budget_every) RW(pressure_every)
       RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure) RW(sbudget_every)
       RW(ycross_every) RW(ycross_planes) RW(ycross_rows)
-      RW(pdf_every) RW(pdf_planes) RW(pdf_bins) RW(pdf_joint_bins) RW(pdf_span) RW(pdf_vorticity);
+      RW(pdf_every) RW(pdf_planes) RW(pdf_bins) RW(pdf_joint_bins) RW(pdf_span) RW(pdf_vorticity)
+      RW(regrid) RW(regrid_stretch);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -128,6 +130,32 @@ PYBIND11_MODULE(_core, m) {
       .def_property_readonly("d2_wN", [](const YGrid& g) { return std::vector<double>(g.d2_wN, g.d2_wN + 3); })
       .def_readonly("d2_w0_up", &YGrid::d2_w0_up)
       .def_readonly("d2_wN_lo", &YGrid::d2_wN_lo);
+
+  // regridding tables (regrid.hpp), bound like YGrid.build so the CPU tests reach them
+  py::class_<RegridTable>(m, "RegridTable")
+      .def_readonly("NY_s", &RegridTable::NY_s)
+      .def_readonly("NY_d", &RegridTable::NY_d)
+      .def_readonly("W", &RegridTable::W)
+      .def_property_readonly("j0", [](const RegridTable& t) { return py::array_t<int>(t.j0.size(), t.j0.data()); })
+      .def_property_readonly("unit", [](const RegridTable& t) { return py::array_t<int>(t.unit.size(), t.unit.data()); })
+      .def_property_readonly("w",
+                             [](const RegridTable& t) {
+                               py::array_t<double> a({static_cast<py::ssize_t>(t.NY_d), static_cast<py::ssize_t>(t.W)});
+                               std::copy(t.w.begin(), t.w.end(), a.mutable_data());
+                               return a;
+                             })
+      .def_property_readonly("win0", [](const RegridTable& t) { return py::array_t<int>(t.win0.size(), t.win0.data()); })
+      .def_property_readonly("winlen", [](const RegridTable& t) { return py::array_t<int>(t.winlen.size(), t.winlen.data()); })
+      .def("max_window", &RegridTable::max_window);
+  m.def("regrid_table", &regrid_table, py::arg("NY_s"), py::arg("stretch_s"), py::arg("NY_d"), py::arg("stretch_d"));
+  m.def("regrid_mode_map",
+        [](int NX_s, int NZ_s, int NX_d, int NZ_d, int kx0, int nkx_loc) {
+          const RegridModeMap mm = regrid_mode_map(NX_s, NZ_s, NX_d, NZ_d, kx0, nkx_loc);
+          return py::make_tuple(py::array_t<int>(mm.plane.size(), mm.plane.data()), mm.nkz_take);
+        },
+        py::arg("NX_s"), py::arg("NZ_s"), py::arg("NX_d"), py::arg("NZ_d"), py::arg("kx0"), py::arg("nkx_loc"),
+        "(source plane of every local target kx or -1, count of kz columns taken)");
+  m.attr("regrid_lds_bytes") = kRegridLdsBytes;
 
   py::class_<Split>(m, "Split")
       .def_static("balanced", &Split::balanced)
@@ -244,6 +272,21 @@ PYBIND11_MODULE(_core, m) {
       .def("transforms_debug", &Solver::transforms_debug, py::call_guard<py::gil_scoped_release>())
       .def("write_restart", &Solver::write_restart, py::call_guard<py::gil_scoped_release>())
       .def("read_restart", &Solver::read_restart, py::call_guard<py::gil_scoped_release>())
+      .def("read_restart_regrid", &Solver::read_restart_regrid, py::arg("g"), py::arg("ddv"), py::arg("umean") = "-",
+           py::arg("src_stretch") = 0.0, py::call_guard<py::gil_scoped_release>())
+      .def("regrid_state",
+           [](Solver& s, py::array_t<std::complex<double>, py::array::c_style | py::array::forcecast> phi,
+              py::array_t<std::complex<double>, py::array::c_style | py::array::forcecast> om,
+              py::array_t<double, py::array::c_style | py::array::forcecast> U, int NX, int NY, int NZ, double stretch) {
+             const size_t n = static_cast<size_t>(NY) * (2 * (NX / 3) + 1) * ((2 * NZ - 2) / 3 + 1);
+             CH_CHECK(NX >= 3 && NY >= 5 && NZ >= 2 && static_cast<size_t>(phi.size()) == n && static_cast<size_t>(om.size()) == n,
+                      "regrid_state: source arrays must have NY*nkx*nkz elements of the source grid");
+             CH_CHECK(U.size() == NY, "regrid_state: U must have the source's NY elements");
+             py::gil_scoped_release r;
+             s.regrid_state(phi.data(), om.data(), U.data(), NX, NY, NZ, stretch);
+           },
+           py::arg("phi"), py::arg("omega"), py::arg("U"), py::arg("NX"), py::arg("NY"), py::arg("NZ"), py::arg("stretch"))
+      .def("regrid_timing", &Solver::regrid_timing)
       .def("checkpoint_async", &Solver::checkpoint_async, py::call_guard<py::gil_scoped_release>())
       .def("wait_checkpoint", &Solver::wait_checkpoint, py::call_guard<py::gil_scoped_release>())
       .def("barrier", &Solver::barrier, py::call_guard<py::gil_scoped_release>())

@@ -241,6 +241,8 @@ Config Config::from_tree(const ConfigTree& t) {
   c.pdf_joint_bins = static_cast<int>(t.get_int(pick(t, "pdf_joint_bins"), c.pdf_joint_bins));
   c.pdf_span = t.get_double(pick(t, "pdf_span"), c.pdf_span);
   c.pdf_vorticity = static_cast<int>(t.get_int(pick(t, "pdf_vorticity"), c.pdf_vorticity));
+  c.regrid = t.get_bool(pick(t, "regrid"), c.regrid);
+  c.regrid_stretch = t.get_double(pick(t, "regrid_stretch"), c.regrid_stretch);
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -378,6 +380,7 @@ void Config::validate() const {
            "pdf_joint_bins must divide pdf_bins and be at most 64");
   CH_CHECK(pdf_span > 0, "pdf_span must be positive");
   CH_CHECK(pdf_vorticity == 0 || pdf_vorticity == 1, "pdf_vorticity must be 0|1");
+  CH_CHECK(regrid_stretch >= 0, "regrid_stretch must be >= 0 (0 = from the file)");
 }
 
 std::string Config::to_string() const {
@@ -416,6 +419,7 @@ std::string Config::to_string() const {
   o << "  pdf_every = " << pdf_every << ";\n  pdf_planes = \"" << pdf_planes << "\";\n";
   o << "  pdf_bins = " << pdf_bins << ";\n  pdf_joint_bins = " << pdf_joint_bins << ";\n";
   o << "  pdf_span = " << pdf_span << ";\n  pdf_vorticity = " << pdf_vorticity << ";\n";
+  o << "  regrid = " << (regrid ? "true" : "false") << ";\n  regrid_stretch = " << regrid_stretch << ";\n";
   o << "};\n";
   return o.str();
 }

@@ -210,7 +210,7 @@ std::map<std::string, double> h5_read_attrs(const std::string& path) {
   H5& h = h5();
   std::map<std::string, double> out;
   Hid f(h.Fopen(path.c_str(), ACC_RDONLY, P_DEFAULT), h.Fclose, "open " + path);
-  static const char* keys[] = {"time", "dt", "step", "Re", "Q", "LX", "LZ", "NX", "NY", "NZ", "format_version"};
+  static const char* keys[] = {"time", "dt", "step", "Re", "Q", "LX", "LZ", "NX", "NY", "NZ", "format_version", "stretch"};
   for (const char* k : keys) {
     if (h.Aexists(f.id, k) <= 0) continue;
     Hid a(h.Aopen(f.id, k, P_DEFAULT), h.Aclose, std::string("attribute ") + k);

@@ -2358,7 +2358,7 @@ void Solver::write_restart_job(const RestartJob& j, const std::function<void(int
                                          {"Re", cfg_.Re},  {"Q", cfg_.Q},   {"LX", cfg_.LX},
                                          {"LZ", cfg_.LZ},  {"NX", double(p.NX)}, {"NY", double(N)},
                                          {"NZ", double(NZ)}, {"format_version", 2.0},
-                                         {"fp64", fp64_ ? 1.0 : 0.0}};
+                                         {"fp64", fp64_ ? 1.0 : 0.0}, {"stretch", cfg_.stretch}};
   int stage = 0;
   for (int which = 0; which < 2; ++which) {
     const std::string& path = which == 0 ? j.g : j.ddv;
@@ -2466,6 +2466,10 @@ void Solver::wait_checkpoint() {
 }
 
 void Solver::read_restart(const std::string& g, const std::string& ddv, const std::string& umean) {
+  if (cfg_.regrid) {  // files on any grid of the same box (regrid.cpp)
+    read_restart_regrid(g, ddv, umean, cfg_.regrid_stretch);
+    return;
+  }
   const Plan& p = plan_;
   const int N = p.NY, NZ = p.NZ, lines = p.lines_loc();
   const double N2 = static_cast<double>(p.NX) * p.Nzp;

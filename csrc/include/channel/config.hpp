@@ -105,6 +105,9 @@ struct Config {
   int pdf_joint_bins = 64;             // bins per axis of the joint histogram (divides pdf_bins, at most 64)
   double pdf_span = 8.0;               // half-width of the binned range in plane r.m.s.
   int pdf_vorticity = 0;               // 1 = also omega_x, omega_y, omega_z
+  // Restart onto another grid (regrid.hpp): the input files may be on any grid of the same box
+  bool regrid = false;                 // false: a file on another grid is refused
+  double regrid_stretch = 0.0;         // the input files' tanh stretching (0 = the file's "stretch" attribute, else `stretch`)
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});

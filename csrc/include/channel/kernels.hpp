@@ -485,6 +485,35 @@ struct YCrossArgs : SpecWalkArgs {    // u, v, w; the shear set also omega_x and
   double* ckz = nullptr;              // [nref][kYSpecRows][N][nkz]
 };
 void ycross_accumulate(const YCrossArgs& a, bool fp64, hipStream_t s);
+// Regridding of spectral lines onto the solver's grid (regrid.hpp has the tables; kernels/regrid.hip): the
+// lines of `nkx` consecutive kx of one kx sub-block are read from a line-major fp64 staging buffer
+// [slot][scols][NY_s] (complex; each line contiguous in y), interpolated along y and written
+// line-fastest into the block's spectral field.  A workgroup takes one kx, 8 kz lines and one chunk of
+// kRegridChunk target planes: it stages the chunk's source window of its lines in LDS, then every lane
+// forms one output, value = (sum_m w[y][m] f[j0[y] + m]) / n2 (the unit rows copy f[j0[y] + unit[y]]),
+// rounded once to the storage type.  Local kz lines [ncol, nkzs) are written as zeros; a kx whose slot is
+// negative is left untouched (the caller zeroes the field first).  Destination addressing is spec_index
+// with the geometry of the sub-block.  U (optional): plane y of line (u_ikx, kz 0) becomes (U[y], 0).
+constexpr int kRegridLdsBytes = 64 * 1024;  // the kernel's dynamic LDS budget: 8 lines of (max window | 1) rows
+struct RegridArgs {
+  const double* src = nullptr;        // staging buffer
+  const int* slot = nullptr;          // [nkx] slot of kx ikx0 + i of the sub-block, or -1
+  int nkx = 0, ikx0 = 0;              // kx of this launch, the first one's index in the sub-block
+  int scols = 0, ncol = 0;            // lines per slot; local kz lines with a source (<= scols)
+  int NY_s = 0, NY_d = 0, W = 0;
+  const int* j0 = nullptr;            // [NY_d]
+  const int* unit = nullptr;          // [NY_d]
+  const double* w = nullptr;          // [NY_d][W]
+  const int* win = nullptr;           // [chunks][2]: win0, winlen
+  int max_window = 0;                 // the largest winlen (sizes the LDS)
+  double n2 = 1.0;                    // the source's units (divisor)
+  void* dst = nullptr;                // the sub-block's field
+  int nkx_blk = 0, nkzs = 0, kzb = 0;  // spec_index geometry of the sub-block
+  const double* U = nullptr;          // [NY_d] mean profile for line (u_ikx, 0), or null
+  int u_ikx = -1;
+  int lds_poison = 0;                 // debug: fill the LDS with NaN before use
+};
+void regrid_launch(const RegridArgs& a, bool fp64, hipStream_t s);
 // element (local kx 0, kz 0) of every plane y < N of one spectral field (lines = nkx_loc * nkzs) := 0
 void zero_mean_line(void* q, int N, int kzb, int lines, bool fp64, hipStream_t s);
 // fault injection (tests): element `elem` of a complex field becomes NaN

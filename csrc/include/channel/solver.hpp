@@ -222,6 +222,19 @@ class Solver {
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
   void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
   void read_restart(const std::string& g, const std::string& ddv, const std::string& umean);
+  // ---- restart onto another grid (regrid.cpp; regrid.hpp has the semantics) ---------------
+  // Files on any grid of the same box: modes map by index (truncated or zero-padded), every line is
+  // interpolated along y on the device, U(y) with the same table on the host.  read_restart calls it
+  // when cfg.regrid is set.  src_stretch: the files' tanh stretching (0: their "stretch" attribute,
+  // else the config's).  time and step are restored; dt only when the grid is unchanged.
+  void read_restart_regrid(const std::string& g, const std::string& ddv, const std::string& umean, double src_stretch = 0.0);
+  // The same from a global source state in memory, in the canonical one-rank get_state layout
+  // [NY_s][nkx_s][nkz_s] (true Fourier coefficients); every rank picks its own lines.  The clock is
+  // left as it is.
+  void regrid_state(const std::complex<double>* phi_s, const std::complex<double>* om_s, const double* U_s, int NX_s, int NY_s,
+                    int NZ_s, double stretch_s);
+  // host and device times in ms of the last regrid: [source read / reorder, upload, kernel, total]
+  std::vector<double> regrid_timing() const { return regrid_ms_; }
   // capture the state now (host copy) and write the files from a background thread; the next
   // checkpoint / wait_checkpoint() / run() end / destructor joins it (and rethrows its error)
   void checkpoint_async(const std::string& g, const std::string& ddv, const std::string& umean);
@@ -347,6 +360,19 @@ class Solver {
   RestartJob capture_restart(const std::string& g, const std::string& ddv, const std::string& umean);
   // turn(t) is called before every rank-ordered write step t (t % P = the writing rank)
   void write_restart_job(const RestartJob& j, const std::function<void(int)>& turn);
+  // a regrid source: its grid and units, and fill(field 0 phi | 1 omega, local target kx of a batch,
+  // host) staging the batch's source planes, each plane_lines lines [kz][y] of (re, im) doubles of
+  // which lines [line0, line0 + local kz with a source) are uploaded
+  struct RegridSource {
+    int NX = 0, NY = 0, NZ = 0;
+    double stretch = 2.0, n2 = 1.0;
+    size_t plane_lines = 0;
+    int line0 = 0;
+    std::function<void(int, const std::vector<int>&, std::vector<double>&)> fill;
+    std::vector<double> U;  // [NY] mean profile on the target grid (true units)
+  };
+  void regrid_apply(const RegridSource& src);
+  std::vector<double> regrid_ms_;
 
   Config cfg_;
   Plan plan_;
