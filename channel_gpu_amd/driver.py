@@ -40,7 +40,7 @@ def main(argv=None) -> int:
         print(f"\nchannel_gpu_amd: {n} RK3 steps on {world} rank(s) in {sec:.3f} s "
               f"({1e3 * sec / max(n, 1):.3f} ms/step, {pts * n / max(sec, 1e-30):.3e} grid-pts/s)")
     if cfg.out_G != "-" and cfg.out_DDV != "-":
-        flow.save(cfg.out_G, cfg.out_DDV, cfg.out_UMEAN)
+        flow.save(cfg.out_G, cfg.out_DDV, cfg.out_UMEAN, cfg.out_T if cfg.scalar else "-")
     return 0
 
 

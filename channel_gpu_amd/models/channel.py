@@ -73,7 +73,7 @@ class ChannelFlow:
     def initialize(self):
         c = self.cfg
         if c.ic == "file":
-            self.solver.read_restart(c.in_G, c.in_DDV, c.in_UMEAN)
+            self.solver.read_restart(c.in_G, c.in_DDV, c.in_UMEAN, c.in_T if c.scalar else "-")
         else:
             self.solver.init_ic()
         self.solver.prepare()
@@ -85,6 +85,20 @@ class ChannelFlow:
 
     def get_state(self):
         return self.solver.get_state()
+
+    # ---- passive scalar (``scalar = true``; one rank without a communicator) ----------------------
+    def set_scalar(self, theta):
+        """Set theta-hat, ``(NY, nkx, nkz)`` complex like the state; its mean line (kx, kz) = (0, 0) is the
+        real mean profile Theta(y).  R_theta is cleared."""
+        self.solver.set_scalar(np.asarray(theta, complex))
+
+    def get_scalar(self) -> np.ndarray:
+        return np.asarray(self.solver.get_scalar())
+
+    def scalar_sums(self) -> np.ndarray:
+        """``ndarray (5, NY)``: Theta, <theta'theta'>, <u'theta'>, <v theta'>, <w theta'> of the current
+        state (Parseval plane sums over the retained modes, the weights of ``stats``)."""
+        return np.asarray(self.solver.scalar_sums())
 
     # ---- stepping ---------------------------------------------------------------------------
     def step(self, n: int = 1):
@@ -101,19 +115,23 @@ class ChannelFlow:
         return self.solver.log()
 
     # ---- output ------------------------------------------------------------------------------
-    def save(self, g: str, ddv: str, umean: str = "-"):
-        self.solver.write_restart(g, ddv, umean)
+    def save(self, g: str, ddv: str, umean: str = "-", t: str = "-"):
+        """Write a restart; ``t``: also theta, in a file with the layout, units and attributes of ``g``."""
+        self.solver.write_restart(g, ddv, umean, t)
 
-    def load(self, g: str, ddv: str, umean: str = "-", regrid: bool = False, src_stretch: float | None = None):
+    def load(self, g: str, ddv: str, umean: str = "-", regrid: bool = False, src_stretch: float | None = None,
+             t: str = "-"):
         """Read a restart.  ``regrid`` (or the config key of that name): the files may be on another
         grid of the same box; modes map by index and every line is interpolated along y on the device
         (README "Restarting on another grid").  ``src_stretch``: the files' tanh stretching (default:
         the config's ``regrid_stretch``, else the files' ``stretch`` attribute, else the config's)."""
         if regrid or self.cfg.regrid:
+            if t != "-":
+                raise ValueError("load: regrid with t= is not supported (theta restarts on its own grid only)")
             s = self.cfg.regrid_stretch if src_stretch is None else float(src_stretch)
             self.solver.read_restart_regrid(g, ddv, umean, s)
         else:
-            self.solver.read_restart(g, ddv, umean)
+            self.solver.read_restart(g, ddv, umean, t)
         self.solver.prepare()
 
     def regrid_from(self, phi, omega, U, *, NX: int, NY: int, NZ: int, stretch: float | None = None):

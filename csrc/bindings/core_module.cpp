@@ -104,7 +104,8 @@ PYBIND11_MODULE(_core, m) {
       RW(pstrain_every) RW(yspectra_every) RW(yspectra_pressure) RW(sbudget_every)
       RW(ycross_every) RW(ycross_planes) RW(ycross_rows)
       RW(pdf_every) RW(pdf_planes) RW(pdf_bins) RW(pdf_joint_bins) RW(pdf_span) RW(pdf_vorticity)
-      RW(regrid) RW(regrid_stretch);
+      RW(regrid) RW(regrid_stretch)
+      RW(scalar) RW(Pr) RW(scalar_lower) RW(scalar_upper) RW(scalar_source) RW(scalar_ic) RW(in_T) RW(out_T) RW(scalar_every);
 #undef RW
 
   m.def("parse_config_tree", [](const std::string& text) { return ConfigTree::parse_string(text).items(); });
@@ -242,6 +243,40 @@ PYBIND11_MODULE(_core, m) {
              return py::make_tuple(phi, om, U);
            })
       .def("init_ic", &Solver::init_ic, py::call_guard<py::gil_scoped_release>())
+      .def("scalar_on", &Solver::scalar_on)
+      .def("set_scalar",
+           [](Solver& s, py::array_t<std::complex<double>, py::array::c_style | py::array::forcecast> th) {
+             CH_CHECK(static_cast<size_t>(th.size()) == s.plan().spec_elems(), "theta must have NY*nkx_loc*nkz_loc elements");
+             py::gil_scoped_release r;
+             s.set_scalar(th.data());
+           },
+           "theta-hat, canonical (NY, nkx, nkz); the mean line (kx, kz) = (0, 0) is the mean profile Theta(y)")
+      .def("get_scalar",
+           [](Solver& s) {
+             const Plan& p = s.plan();
+             py::array_t<std::complex<double>> th({p.NY, p.nkx_loc, p.nkz_loc});
+             s.get_scalar(th.mutable_data());
+             return th;
+           })
+      .def("init_scalar_ic", &Solver::init_scalar_ic, py::call_guard<py::gil_scoped_release>())
+      .def("scalar_flux_hat",
+           [](Solver& s) {
+             std::vector<std::complex<double>> v;
+             {
+               py::gil_scoped_release r;
+               v = s.scalar_flux_hat();
+             }
+             const Plan& p = s.plan();
+             py::array_t<std::complex<double>> a({static_cast<py::ssize_t>(3), static_cast<py::ssize_t>(p.NY),
+                                                  static_cast<py::ssize_t>(p.nkx_loc), static_cast<py::ssize_t>(p.nkz_loc)});
+             std::copy(v.begin(), v.end(), a.mutable_data());
+             return a;
+           },
+           "the flux pass alone: (u theta)^, (v theta)^, (w theta)^ of the current state, (3, NY, nkx, nkz)")
+      .def("scalar_sums", [](Solver& s) { return profile_rows(s, &Solver::scalar_sums, 5); },
+           "(5, NY): Theta, <theta'theta'>, <u'theta'>, <v theta'>, <w theta'>")
+      .def("scalar_timing", &Solver::scalar_timing, py::call_guard<py::gil_scoped_release>(),
+           "device ms of one substep's scalar work: x-backward, zscalar, x-forward, scalar_kernel")
       .def("prepare", &Solver::prepare, py::call_guard<py::gil_scoped_release>())
       .def("step", &Solver::step, py::arg("stats_for_next") = false, py::call_guard<py::gil_scoped_release>())
       .def("run", &Solver::run, py::arg("nsteps"), py::arg("verbose") = true, py::call_guard<py::gil_scoped_release>())
@@ -270,8 +305,10 @@ PYBIND11_MODULE(_core, m) {
       .def("symmetrize", &Solver::symmetrize)
       .def("substep_debug", &Solver::substep_debug, py::call_guard<py::gil_scoped_release>())
       .def("transforms_debug", &Solver::transforms_debug, py::call_guard<py::gil_scoped_release>())
-      .def("write_restart", &Solver::write_restart, py::call_guard<py::gil_scoped_release>())
-      .def("read_restart", &Solver::read_restart, py::call_guard<py::gil_scoped_release>())
+      .def("write_restart", &Solver::write_restart, py::arg("g"), py::arg("ddv"), py::arg("umean") = "-", py::arg("t") = "-",
+           py::call_guard<py::gil_scoped_release>())
+      .def("read_restart", &Solver::read_restart, py::arg("g"), py::arg("ddv"), py::arg("umean") = "-", py::arg("t") = "-",
+           py::call_guard<py::gil_scoped_release>())
       .def("read_restart_regrid", &Solver::read_restart_regrid, py::arg("g"), py::arg("ddv"), py::arg("umean") = "-",
            py::arg("src_stretch") = 0.0, py::call_guard<py::gil_scoped_release>())
       .def("regrid_state",
@@ -287,7 +324,8 @@ PYBIND11_MODULE(_core, m) {
            },
            py::arg("phi"), py::arg("omega"), py::arg("U"), py::arg("NX"), py::arg("NY"), py::arg("NZ"), py::arg("stretch"))
       .def("regrid_timing", &Solver::regrid_timing)
-      .def("checkpoint_async", &Solver::checkpoint_async, py::call_guard<py::gil_scoped_release>())
+      .def("checkpoint_async", &Solver::checkpoint_async, py::arg("g"), py::arg("ddv"), py::arg("umean") = "-",
+           py::arg("t") = "-", py::call_guard<py::gil_scoped_release>())
       .def("wait_checkpoint", &Solver::wait_checkpoint, py::call_guard<py::gil_scoped_release>())
       .def("barrier", &Solver::barrier, py::call_guard<py::gil_scoped_release>())
       .def("max_over_ranks", &Solver::max_over_ranks, py::call_guard<py::gil_scoped_release>())

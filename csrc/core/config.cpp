@@ -243,6 +243,16 @@ Config Config::from_tree(const ConfigTree& t) {
   c.pdf_vorticity = static_cast<int>(t.get_int(pick(t, "pdf_vorticity"), c.pdf_vorticity));
   c.regrid = t.get_bool(pick(t, "regrid"), c.regrid);
   c.regrid_stretch = t.get_double(pick(t, "regrid_stretch"), c.regrid_stretch);
+  c.scalar = t.get_bool(pick(t, "scalar"), c.scalar);
+  c.Pr = t.get_double(pick(t, "Pr"), c.Pr);
+  c.scalar_lower = t.get_double(pick(t, "scalar_lower"), c.scalar_lower);
+  c.scalar_upper = t.get_double(pick(t, "scalar_upper"), c.scalar_upper);
+  c.scalar_source = t.get_double(pick(t, "scalar_source"), c.scalar_source);
+  c.scalar_ic = t.get_string(pick(t, "scalar_ic"), c.scalar_ic);
+  c.in_T = t.get_string(pick(t, "input.T"), c.in_T);
+  c.out_T = t.get_string(pick(t, "output.T"), c.out_T);
+  c.scalar_every = static_cast<int>(t.get_int(pick(t, "scalar_every"), c.scalar_every));
+  if (c.in_T != "-" && !t.has(pick(t, "scalar_ic"))) c.scalar_ic = "file";
   // Reference semantics: input files given => start from file.
   if (c.in_G != "-" && c.in_DDV != "-" && !t.has(pick(t, "ic"))) c.ic = "file";
   c.validate();
@@ -381,6 +391,12 @@ void Config::validate() const {
   CH_CHECK(pdf_span > 0, "pdf_span must be positive");
   CH_CHECK(pdf_vorticity == 0 || pdf_vorticity == 1, "pdf_vorticity must be 0|1");
   CH_CHECK(regrid_stretch >= 0, "regrid_stretch must be >= 0 (0 = from the file)");
+  CH_CHECK(Pr > 0, "Pr must be positive");
+  CH_CHECK(scalar_ic == "laminar" || scalar_ic == "zero" || scalar_ic == "file", "scalar_ic must be laminar|zero|file");
+  CH_CHECK(scalar_every >= 0, "scalar_every must be >= 0");
+  CH_CHECK(scalar || scalar_every == 0, "scalar_every needs scalar = true");
+  CH_CHECK(scalar || (in_T == "-" && out_T == "-"), "input.T / output.T need scalar = true");
+  CH_CHECK(!(regrid && in_T != "-"), "regrid with input.T: regridding the scalar is not supported (theta restarts on its own grid only)");
 }
 
 std::string Config::to_string() const {
@@ -388,8 +404,8 @@ std::string Config::to_string() const {
   o.precision(17);
   o << "application:\n{\n";
   o << "  NX = " << NX << ";\n  NY = " << NY << ";\n  NZ = " << NZ << ";\n";
-  o << "  input:\n  {\n    G = \"" << in_G << "\";\n    DDV = \"" << in_DDV << "\";\n    UMEAN = \"" << in_UMEAN << "\";\n  };\n";
-  o << "  output:\n  {\n    G = \"" << out_G << "\";\n    DDV = \"" << out_DDV << "\";\n    UMEAN = \"" << out_UMEAN << "\";\n  };\n";
+  o << "  input:\n  {\n    G = \"" << in_G << "\";\n    DDV = \"" << in_DDV << "\";\n    UMEAN = \"" << in_UMEAN << "\";\n    T = \"" << in_T << "\";\n  };\n";
+  o << "  output:\n  {\n    G = \"" << out_G << "\";\n    DDV = \"" << out_DDV << "\";\n    UMEAN = \"" << out_UMEAN << "\";\n    T = \"" << out_T << "\";\n  };\n";
   o << "  path = \"" << path << "\";\n";
   o << "  Re = " << Re << ";\n  Q = " << Q << ";\n  LX = " << LX << ";\n  LZ = " << LZ << ";\n";
   o << "  stretch = " << stretch << ";\n  nsteps = " << nsteps << ";\n  t_end = " << t_end << ";\n";
@@ -420,6 +436,10 @@ std::string Config::to_string() const {
   o << "  pdf_bins = " << pdf_bins << ";\n  pdf_joint_bins = " << pdf_joint_bins << ";\n";
   o << "  pdf_span = " << pdf_span << ";\n  pdf_vorticity = " << pdf_vorticity << ";\n";
   o << "  regrid = " << (regrid ? "true" : "false") << ";\n  regrid_stretch = " << regrid_stretch << ";\n";
+  o << "  scalar = " << (scalar ? "true" : "false") << ";\n  Pr = " << Pr << ";\n";
+  o << "  scalar_lower = " << scalar_lower << ";\n  scalar_upper = " << scalar_upper << ";\n";
+  o << "  scalar_source = " << scalar_source << ";\n  scalar_ic = \"" << scalar_ic << "\";\n";
+  o << "  scalar_every = " << scalar_every << ";\n";
   o << "};\n";
   return o.str();
 }

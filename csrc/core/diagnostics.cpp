@@ -176,15 +176,16 @@ std::vector<int> Solver::all_planes() const {
   return ys;
 }
 
-// The pressure mode of the export: the x-backward of Pi (field 0 of d_pres_) for the planes of the chunk
-// (xc, sc) into slot 3 of the scratch; returns its single-field arguments.
-XArgs Solver::pi_backward(const XArgs& xc, const XSrc& sc) {
+// The pressure mode of the export: the x-backward of one spectral field (default Pi, field 0 of d_pres_;
+// the scalar's flux pass: theta) for the planes of the chunk (xc, sc) into slot 3 of the scratch; returns
+// its single-field arguments.  The field's mean line is transformed as it is.
+XArgs Solver::pi_backward(const XArgs& xc, const XSrc& sc, const void* field) {
   XArgs xp = xc;
   xp.nfields = 1;
   xp.combine = 0;
   xp.zero_mean_field = -1;
   XSrc sp;
-  sp.base = static_cast<const char*>(d_pres_) + (static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
+  sp.base = static_cast<const char*>(field ? field : d_pres_) + (static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
   sp.nsrc = 1;
   sp.kx_start[0] = 0;
   sp.kx_start[1] = plan_.nkx;
@@ -853,6 +854,106 @@ void Solver::write_pstrain_files() {
   const int N = plan_.NY;
   const char* names[4] = {"PS_UU.dat", "PS_VV.dat", "PS_WW.dat", "PS_UV.dat"};
   for (int q = 0; q < 4; ++q) append_profile(cfg_.path + names[q], m.data() + static_cast<size_t>(q) * N, N);
+}
+
+// ---- passive scalar ------------------------------------------------------------------------------------
+std::vector<std::complex<double>> Solver::scalar_flux_hat() {
+  CH_CHECK(sc_, "scalar_flux_hat: scalar = false");
+  if (!prepared_) prepare();
+  scalar_flux_device();
+  std::vector<std::complex<double>> out;
+  out.reserve(3 * canon_);
+  for (int c = 0; c < 3; ++c) {
+    const std::vector<std::complex<double>> h = spec_to_canonical(scalar_ptr(2 + c), "scalar flux");
+    out.insert(out.end(), h.begin(), h.end());
+  }
+  return out;
+}
+
+// Row 0 is the mean line of theta itself; rows 1..4 one more operation of the shared spectral walk, with
+// theta in the place of p-hat' and K-SPEC's outputs read in place (the combine mode's as the spectra do).
+std::vector<double> Solver::scalar_sums() {
+  CH_CHECK(sc_ && !comm_, "scalar_sums: scalar = true on one rank without a communicator");
+  const size_t N = static_cast<size_t>(plan_.NY), n = static_cast<size_t>(kScalarSumRows) * N;
+  if (!d_ssum_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_ssum_), n * sizeof(double)));
+  if (!prepared_) prepare();
+  HIP_CHECK(hipMemsetAsync(d_ssum_, 0, n * sizeof(double), s_comp_));
+  ScalarSumArgs a;
+  walk_args(a, 1u | 2u | 4u, false);
+  a.p = scalar_ptr(0);
+  a.sums = d_ssum_;
+  for_kblocks([&](size_t off, int cnt, int kx0) { scalarsum_accumulate(at_block(a, off, cnt, kx0), fp64_, s_comp_); });
+  std::vector<double> g(n + N);
+  reduce_fetch(d_ssum_, n, g.data() + N);
+  // Theta: the NY elements of the mean line alone, element (y, 0, 0) of either layout (strided copies: the
+  // planes of the plain layout; row y % 8 of every 8-plane tile of the blocked one)
+  std::vector<char> h(N * esz_);
+  const size_t lines = static_cast<size_t>(plan_.nkx_loc) * nkzs_;
+  const int nb = kzb_ ? kSpecYBlock : 1;
+  for (int b = 0; b < nb && b < plan_.NY; ++b) {
+    const size_t rows = (N - b + nb - 1) / nb;
+    HIP_CHECK(hipMemcpy2DAsync(h.data() + b * esz_, nb * esz_, static_cast<const char*>(scalar_ptr(0)) + dev_index(b, 0, 0) * esz_,
+                               nb * lines * esz_, esz_, rows, hipMemcpyDeviceToHost, s_comp_));
+  }
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  for (size_t j = 0; j < N; ++j)
+    g[j] = fp64_ ? reinterpret_cast<const double2*>(h.data())[j].x : static_cast<double>(reinterpret_cast<const float2*>(h.data())[j].x);
+  return g;
+}
+
+std::vector<double> Solver::scalar_timing() {
+  CH_CHECK(sc_, "scalar_timing: scalar = false");
+  if (!prepared_) prepare();
+  std::vector<double> ms(4, 0.0);
+  scalar_flux_device(ms.data());
+  // the advance on a copy's worth of state: theta and R_theta are put back afterwards
+  const size_t fb = spec_ * esz_;
+  void* keep = nullptr;
+  HIP_CHECK(hipMalloc(&keep, 2 * fb));
+  HIP_CHECK(hipMemcpyAsync(keep, scalar_ptr(0), 2 * fb, hipMemcpyDeviceToDevice, s_comp_));
+  hipEvent_t e0, e1;
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, s_comp_));
+  scalar_advance_device(0);
+  HIP_CHECK(hipEventRecord(e1, s_comp_));
+  HIP_CHECK(hipMemcpyAsync(scalar_ptr(0), keep, 2 * fb, hipMemcpyDeviceToDevice, s_comp_));
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  float t = 0;
+  HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+  ms[3] = t;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipFree(keep);
+  return ms;
+}
+
+// one line of NY values per call and file, as write_stats_files: Theta, the scalar r.m.s., <u'theta'>,
+// <v theta'>; TWALL.dat: step, time and the wall derivatives of Theta by the compact D1 (on the host)
+void Solver::write_scalar_files() {
+  const std::vector<double> m = scalar_sums();
+  const int N = plan_.NY;
+  append_profile(cfg_.path + "TMEAN.dat", m.data(), N);
+  append_profile(cfg_.path + "TRMS.dat", m.data() + N, N, 1.0, true);
+  append_profile(cfg_.path + "UT.dat", m.data() + 2 * N, N);
+  append_profile(cfg_.path + "VT.dat", m.data() + 3 * N, N);
+  // D1 Theta: tridiag(d1_lo, 1, d1_up) f' = B1 Theta
+  const YGrid& g = grid_;
+  std::vector<double> r(N), cp(N);
+  const double* f = m.data();
+  r[0] = g.d1_w0[0] * f[0] + g.d1_w0[1] * f[1] + g.d1_w0[2] * f[2];
+  r[N - 1] = g.d1_wN[0] * f[N - 1] + g.d1_wN[1] * f[N - 2] + g.d1_wN[2] * f[N - 3];
+  for (int j = 1; j < N - 1; ++j) r[j] = g.d1_rm[j] * f[j - 1] + g.d1_rc[j] * f[j] + g.d1_rp[j] * f[j + 1];
+  cp[0] = g.d1_up[0];
+  for (int j = 1; j < N; ++j) {
+    const double mj = 1.0 - g.d1_lo[j] * cp[j - 1];
+    cp[j] = g.d1_up[j] / mj;
+    r[j] = (r[j] - g.d1_lo[j] * r[j - 1]) / mj;
+  }
+  for (int j = N - 2; j >= 0; --j) r[j] -= cp[j] * r[j + 1];
+  std::ofstream tw(cfg_.path + "TWALL.dat", std::ios::app);
+  tw.precision(10);
+  tw << nstep_ << " " << std::scientific << time() << " " << r[0] << " " << r[N - 1] << "\n";
 }
 
 std::vector<double> Solver::gradient_sums() {

@@ -162,8 +162,10 @@ Solver::Solver(const Config& cfg, int rank, int nranks, int device, const std::s
   {
     int R = 1, H = 1;
     kspec_geometry(cfg_.NY, fp64_, R, H);
+    CH_CHECK(!cfg_.scalar || H == 1, "scalar = true: the scalar's y-line kernel runs one wave per line (not with CHANNEL_KSPEC_HALVES=1)");
     ytab_.upload(grid_, R, s_comp_, H);
   }
+  CH_CHECK(!comm_ || !cfg_.scalar, "scalar = true: the passive scalar is single-rank (one rank without a communicator)");
   CH_CHECK(!comm_ || (cfg_.fields_every == 0 && cfg_.moments_every == 0),
            "fields_every / moments_every: the physical-space export is single-rank (one rank without a communicator)");
   tw_x_.build(plan_.NX, fp64_);
@@ -297,6 +299,10 @@ void Solver::alloc() {
   HIP_CHECK(hipMalloc(&phys_, std::max<size_t>(6 * physn_, 1) * esz_));
   HIP_CHECK(hipMemset(state_, 0, 3 * spec_ * esz_));
   HIP_CHECK(hipMemset(out_, 0, 6 * spec_ * esz_));
+  if (cfg_.scalar) {  // theta, R_theta and the three flux fields
+    HIP_CHECK(hipMalloc(&sc_, 5 * spec_ * esz_));
+    HIP_CHECK(hipMemset(sc_, 0, 5 * spec_ * esz_));
+  }
   if (comm_) {
     HIP_CHECK(hipMalloc(&xbuf_, 6 * xstride_ * esz_));
     HIP_CHECK(hipMemset(xbuf_, 0, 6 * xstride_ * esz_));
@@ -458,11 +464,13 @@ void Solver::free_all() {
     if (e) (void)hipEventDestroy(e);
   if (h_tdt_) (void)hipHostFree(h_tdt_);
   h_tdt_ = nullptr;
-  for (void* p : {state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
+  for (void* p : {sc_, static_cast<void*>(d_ssum_), state_, out_, phys_, xbuf_, zbuf_, dscal_, snap_, d_spec_, d_sym_, static_cast<void*>(d_y_),
                   static_cast<void*>(d_rowtab_), d_real_, static_cast<void*>(d_mom_),
                   static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_),
                   static_cast<void*>(d_yspec_), d_hist_, static_cast<void*>(d_sbud_), static_cast<void*>(d_ycross_)})
     if (p) (void)hipFree(p);
+  sc_ = nullptr;
+  d_ssum_ = nullptr;
   d_pstr_ = nullptr;
   d_yspec_ = nullptr;
   d_sbud_ = nullptr;
@@ -556,6 +564,7 @@ void Solver::set_state(const std::complex<double>* phi, const std::complex<doubl
     HIP_CHECK(hipMemcpy(field_ptr(OMEGA), h.data(), spec_ * esz_, hipMemcpyHostToDevice));
   }
   HIP_CHECK(hipMemset(field_ptr(RPHI), 0, 2 * spec_ * esz_));
+  if (sc_) HIP_CHECK(hipMemset(scalar_ptr(1), 0, spec_ * esz_));
   prepared_ = false;
 }
 
@@ -673,6 +682,71 @@ void Solver::init_ic() {
   double zero2[2] = {0.0, 0.0};
   HIP_CHECK(hipMemcpy(d_dt_, zero2, 2 * sizeof(double), hipMemcpyHostToDevice));
   nstep_ = 0;
+  if (sc_) init_scalar_ic();
+}
+
+// ---- passive scalar: state ----------------------------------------------------------------------
+void Solver::set_scalar(const std::complex<double>* th) {
+  CH_CHECK(sc_, "set_scalar: scalar = false");
+  const Plan& p = plan_;
+  std::vector<std::complex<double>> b(spec_, 0.0);  // canonical -> device layout (padding: 0)
+  for (int y = 0; y < p.NY; ++y)
+    for (int i = 0; i < p.nkx_loc; ++i)
+      for (int k = 0; k < p.nkz_loc; ++k) b[dev_index(y, i, k)] = th[(static_cast<size_t>(y) * p.nkx_loc + i) * p.nkz_loc + k];
+  // the mean line is real
+  for (int y = 0; y < p.NY; ++y) b[dev_index(y, 0, 0)] = b[dev_index(y, 0, 0)].real();
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  if (fp64_) {
+    std::vector<double2> h;
+    to_dev_type(b.data(), spec_, h);
+    HIP_CHECK(hipMemcpy(scalar_ptr(0), h.data(), spec_ * esz_, hipMemcpyHostToDevice));
+  } else {
+    std::vector<float2> h;
+    to_dev_type(b.data(), spec_, h);
+    HIP_CHECK(hipMemcpy(scalar_ptr(0), h.data(), spec_ * esz_, hipMemcpyHostToDevice));
+  }
+  HIP_CHECK(hipMemset(scalar_ptr(1), 0, spec_ * esz_));
+}
+
+void Solver::get_scalar(std::complex<double>* th) const {
+  CH_CHECK(sc_, "get_scalar: scalar = false");
+  const Plan& p = plan_;
+  HIP_CHECK(hipStreamSynchronize(s_comp_));
+  std::vector<std::complex<double>> t(spec_);
+  if (fp64_) {
+    std::vector<double2> h(spec_);
+    HIP_CHECK(hipMemcpy(h.data(), scalar_ptr(0), spec_ * esz_, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
+  } else {
+    std::vector<float2> h(spec_);
+    HIP_CHECK(hipMemcpy(h.data(), scalar_ptr(0), spec_ * esz_, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < spec_; ++i) t[i] = {h[i].x, h[i].y};
+  }
+  for (int y = 0; y < p.NY; ++y)
+    for (int i = 0; i < p.nkx_loc; ++i)
+      for (int k = 0; k < p.nkz_loc; ++k) th[(static_cast<size_t>(y) * p.nkx_loc + i) * p.nkz_loc + k] = t[dev_index(y, i, k)];
+}
+
+// scalar_ic: laminar = the steady conduction profile with the source, Theta = lower + (upper - lower)
+// (y + 1) / 2 + S (1 - y^2) / (2 kappa), every other mode zero; zero; file = input.T
+void Solver::init_scalar_ic() {
+  CH_CHECK(sc_, "init_scalar_ic: scalar = false");
+  if (cfg_.scalar_ic == "file") {
+    CH_CHECK(cfg_.in_T != "-", "scalar_ic = \"file\" needs input.T");
+    read_scalar_file(cfg_.in_T);
+    return;
+  }
+  std::vector<std::complex<double>> th(canon_, 0.0);
+  if (cfg_.scalar_ic == "laminar") {
+    const double kappa = 1.0 / (cfg_.Re * cfg_.Pr);
+    const size_t lines = plan_.lines_loc();
+    for (int j = 0; j < plan_.NY; ++j) {
+      const double y = grid_.y[j];
+      th[static_cast<size_t>(j) * lines] =
+          cfg_.scalar_lower + (cfg_.scalar_upper - cfg_.scalar_lower) * 0.5 * (y + 1.0) + cfg_.scalar_source * (1.0 - y * y) / (2.0 * kappa);
+    }
+  }
+  set_scalar(th.data());
 }
 
 void Solver::set_time(double t, double dt) {
@@ -1661,8 +1735,12 @@ void Solver::prepare() {
 
 void Solver::step_body(bool stats) {
   for (int n = 0; n < 3; ++n) {
+    // passive scalar: the fluxes of the stage state before transforms() overwrites u, v, w with H; the
+    // advance after K-SPEC (it reads the dt of this step)
+    if (sc_) scalar_flux_device();
     transforms(n, false);
     kspec(1, n, stats && n == 2);
+    if (sc_) scalar_advance_device(n);
     CH_CHECK(!capture_fail_test_, "capture failure injected (CHANNEL_TEST_CAPTURE_FAIL)");
   }
   // the next step's substep-0 backward exchange of blocks 0 .. NB-2, behind this step's last
@@ -1852,8 +1930,101 @@ void Solver::step(bool stats_for_next) {
 
 void Solver::substep_debug(int n) {
   if (!prepared_) prepare();
+  if (sc_) scalar_flux_device();
   transforms(n, false);
   kspec(1, n, false);
+  if (sc_) scalar_advance_device(n);
+}
+
+// ---- passive scalar: the two stages of a substep ---------------------------------------------------
+// Flux pass, chunk by chunk as static_return_device(): the x-backward of u, v, w (the combine mode forms
+// all six), theta into slot 3 with its mean line, the z kernel, the x-forward of the three products into
+// the flux fields.  On the compute stream, ahead of the momentum chunks (which wait on ev_spec_), in the
+// scratch they use next.
+void Solver::scalar_flux_device(double* ms) {
+  CH_CHECK(sc_ && !comm_, "scalar: single-rank (one rank without a communicator)");
+  const Plan& p = plan_;
+  const int cap = ychunk_ > 0 && ychunk_ < p.ny_loc ? ychunk_ : p.ny_loc;
+  XArgs xa = x_args();
+  const XSrc src = x_src_local(xa);
+  char* flux = static_cast<char*>(scalar_ptr(2));
+  hipEvent_t te[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (ms)
+    for (hipEvent_t& e : te) HIP_CHECK(hipEventCreate(&e));
+  for (int y0 = 0; y0 < p.NY; y0 += cap) {
+    const int ny = std::min(cap, p.NY - y0);
+    XArgs xc;
+    XSrc sc;
+    x_chunk(xa, src, y0, ny, xc, sc);
+    if (!combine_) xc.nfields = 3;  // (the combine mode forms all six)
+    if (ms) HIP_CHECK(hipEventRecord(te[0], s_comp_));
+    xfft_backward(xc, sc, phys_, tw_x_, fp64_, s_comp_);
+    XArgs xp = pi_backward(xc, sc, scalar_ptr(0));
+    if (ms) HIP_CHECK(hipEventRecord(te[1], s_comp_));
+    ZScalarArgs za;
+    za.NX = p.NX;
+    za.Nzp = p.Nzp;
+    za.nkz = p.nkz;
+    za.ny = ny;
+    za.xpitch = xpitch_;
+    za.field_stride = static_cast<long long>(physn_);
+    za.lds_poison = xa.lds_poison;
+    zscalar(za, phys_, tw_z_, fp64_, s_comp_);
+    if (ms) HIP_CHECK(hipEventRecord(te[2], s_comp_));
+    // (the chunk's planes of the destination, as transforms() addresses them)
+    XDst dc;
+    dc.base = flux + (static_cast<const char*>(sc.base) - static_cast<const char*>(out_));
+    dc.ndst = 1;
+    dc.kx_start[0] = 0;
+    dc.kx_start[1] = p.nkx;
+    xp.nfields = 3;
+    xfft_forward(xp, phys_, dc, tw_x_, fp64_, s_comp_);
+    if (ms) {
+      HIP_CHECK(hipEventRecord(te[3], s_comp_));
+      HIP_CHECK(hipStreamSynchronize(s_comp_));
+      for (int i = 0; i < 3; ++i) {
+        float t = 0;
+        HIP_CHECK(hipEventElapsedTime(&t, te[i], te[i + 1]));
+        ms[i] += t;
+      }
+    }
+  }
+  if (ms)
+    for (hipEvent_t e : te) (void)hipEventDestroy(e);
+}
+
+void Solver::scalar_advance_device(int n) {
+  const Plan& p = plan_;
+  ScalarArgs a;
+  a.N = p.NY;
+  a.lines = p.nkx_loc * nkzs_;
+  a.nkz = nkzs_;
+  a.nkz_real = p.nkz_loc;
+  a.kzb = kzb_;
+  a.kz0 = p.kz0;
+  a.kx0 = p.kx0;
+  a.nkx = p.nkx;
+  a.Kx = p.Kx;
+  a.ax = p.ax;
+  a.az = p.az;
+  a.kappa = 1.0 / (cfg_.Re * cfg_.Pr);
+  a.rk_a = RK3Coef::alpha[n];
+  a.rk_b = RK3Coef::beta[n];
+  a.rk_g = RK3Coef::gamma[n];
+  a.rk_z = RK3Coef::zeta[n];
+  a.store_r = n < 2 ? 1 : 0;  // R of the last substep is never read (zeta[0] = 0)
+  a.dt = d_dt_;
+  a.lower = cfg_.scalar_lower;
+  a.upper = cfg_.scalar_upper;
+  a.source = cfg_.scalar_source;
+  a.th = scalar_ptr(0);
+  a.Rth = scalar_ptr(1);
+  a.fx = scalar_ptr(2);
+  a.fy = scalar_ptr(3);
+  a.fz = scalar_ptr(4);
+  a.health = cfg_.health_check ? d_health_ : nullptr;
+  a.lds_poison = lds_poison_enabled() ? 1 : 0;
+  scalar_advance(ytab_, a, fp64_, s_comp_);
 }
 
 void Solver::transforms_debug(bool dt_upd) {
@@ -2011,6 +2182,7 @@ void Solver::symmetrize() {
   if (!comm_) {
     symmetrize_kz0(field_ptr(PHI), p.NY, p.nkx, nkzs_, p.Kx, kzb_, fp64_, s_comp_);
     symmetrize_kz0(field_ptr(OMEGA), p.NY, p.nkx, nkzs_, p.Kx, kzb_, fp64_, s_comp_);
+    if (sc_) symmetrize_kz0(scalar_ptr(0), p.NY, p.nkx, nkzs_, p.Kx, kzb_, fp64_, s_comp_);
     prepared_ = false;
     return;
   }
@@ -2198,6 +2370,7 @@ void Solver::run(long nsteps, bool verbose) {
     if (cfg_.sbudget_every > 0 && nstep_ % cfg_.sbudget_every == 0) write_sbudget_files();
     if (cfg_.ycross_every > 0 && nstep_ % cfg_.ycross_every == 0) write_ycross_files();
     if (cfg_.pdf_every > 0 && nstep_ % cfg_.pdf_every == 0) write_pdf_files();
+    if (cfg_.scalar_every > 0 && nstep_ % cfg_.scalar_every == 0) write_scalar_files();
     if (ye > 0 && nstep_ % ye == 0) {
       symmetrize();
       prepare();
@@ -2205,8 +2378,9 @@ void Solver::run(long nsteps, bool verbose) {
     if (ce > 0 && nstep_ % ce == 0 && cfg_.out_G != "-") {
       const std::string sfx = "." + std::to_string(nstep_);
       const std::string um = cfg_.out_UMEAN != "-" ? cfg_.out_UMEAN + sfx : "-";
-      if (cfg_.checkpoint_async) checkpoint_async(cfg_.out_G + sfx, cfg_.out_DDV + sfx, um);
-      else write_restart(cfg_.out_G + sfx, cfg_.out_DDV + sfx, um);
+      const std::string tf = sc_ && cfg_.out_T != "-" ? cfg_.out_T + sfx : "-";
+      if (cfg_.checkpoint_async) checkpoint_async(cfg_.out_G + sfx, cfg_.out_DDV + sfx, um, tf);
+      else write_restart(cfg_.out_G + sfx, cfg_.out_DDV + sfx, um, tf);
     }
     if (cfg_.t_end > 0 && t_end_reached()) break;
   }
@@ -2255,8 +2429,9 @@ void Solver::invalidate_graphs() {
 
 void Solver::take_snapshot() {
   const size_t fb = spec_ * esz_;
-  if (!snap_) HIP_CHECK(hipMalloc(&snap_, 2 * fb + 2 * sizeof(double)));
+  if (!snap_) HIP_CHECK(hipMalloc(&snap_, (sc_ ? 3 : 2) * fb + 2 * sizeof(double)));  // (dt, time, then theta)
   char* d = static_cast<char*>(snap_);
+  if (sc_) HIP_CHECK(hipMemcpyAsync(d + 2 * fb + 2 * sizeof(double), scalar_ptr(0), fb, hipMemcpyDeviceToDevice, s_comp_));
   HIP_CHECK(hipMemcpyAsync(d, field_ptr(PHI), fb, hipMemcpyDeviceToDevice, s_comp_));
   HIP_CHECK(hipMemcpyAsync(d + fb, field_ptr(OMEGA), fb, hipMemcpyDeviceToDevice, s_comp_));
   HIP_CHECK(hipMemcpyAsync(d + 2 * fb, d_dt_, 2 * sizeof(double), hipMemcpyDeviceToDevice, s_comp_));
@@ -2272,6 +2447,10 @@ void Solver::rollback() {
   HIP_CHECK(hipMemcpyAsync(field_ptr(OMEGA), d + fb, fb, hipMemcpyDeviceToDevice, s_comp_));
   HIP_CHECK(hipMemcpyAsync(d_dt_, d + 2 * fb, 2 * sizeof(double), hipMemcpyDeviceToDevice, s_comp_));
   HIP_CHECK(hipMemsetAsync(field_ptr(RPHI), 0, 2 * fb, s_comp_));  // zeta_0 = 0: R is not needed at substep 0
+  if (sc_) {
+    HIP_CHECK(hipMemcpyAsync(scalar_ptr(0), d + 2 * fb + 2 * sizeof(double), fb, hipMemcpyDeviceToDevice, s_comp_));
+    HIP_CHECK(hipMemsetAsync(scalar_ptr(1), 0, fb, s_comp_));
+  }
   HIP_CHECK(hipMemsetAsync(d_max_, 0, 4 * sizeof(float), s_comp_));
   HIP_CHECK(hipMemsetAsync(d_health_, 0, sizeof(unsigned), s_comp_));
   HIP_CHECK(hipStreamSynchronize(s_comp_));
@@ -2319,11 +2498,18 @@ void Solver::write_json(const StepLog& L, double ms_per_step) {
 // stepping continues) and the ranks pass the file between them through marker files, so the
 // background writers never touch the communicator.  The reference wrote only at the end, gathering
 // every plane on rank 0 with an MPI_Barrier per plane (hit_mpi.c:257-339, main.c:139-144).
-Solver::RestartJob Solver::capture_restart(const std::string& g, const std::string& ddv, const std::string& umean) {
+Solver::RestartJob Solver::capture_restart(const std::string& g, const std::string& ddv, const std::string& umean,
+                                           const std::string& t) {
   RestartJob j;
   j.g = g;
   j.ddv = ddv;
   j.umean = umean;
+  j.t = t;
+  if (!t.empty() && t != "-") {
+    CH_CHECK(sc_, "restart: a theta file needs scalar = true");
+    j.th.resize(canon_);
+    get_scalar(j.th.data());
+  }
   j.phi.resize(canon_);
   j.om.resize(canon_);
   j.U.resize(plan_.NY);
@@ -2360,8 +2546,8 @@ void Solver::write_restart_job(const RestartJob& j, const std::function<void(int
                                          {"NZ", double(NZ)}, {"format_version", 2.0},
                                          {"fp64", fp64_ ? 1.0 : 0.0}, {"stretch", cfg_.stretch}};
   int stage = 0;
-  for (int which = 0; which < 2; ++which) {
-    const std::string& path = which == 0 ? j.g : j.ddv;
+  for (int which = 0; which < 3; ++which) {  // G (omega_y), DDV (phi), T (theta: its mean line holds Theta)
+    const std::string& path = which == 0 ? j.g : (which == 1 ? j.ddv : j.t);
     if (path.empty() || path == "-") continue;
     for (int r = 0; r < p.P; ++r) {
       turn(stage * p.P + r);
@@ -2383,7 +2569,7 @@ void Solver::write_restart_job(const RestartJob& j, const std::function<void(int
         int dims[3];
         h5_read_planes(path, planes, data, dims);
       }
-      pack(which == 0 ? j.om : j.phi, data);
+      pack(which == 0 ? j.om : (which == 1 ? j.phi : j.th), data);
       h5_write_planes(path, planes, data);
     }
     ++stage;
@@ -2396,17 +2582,17 @@ void Solver::write_restart_job(const RestartJob& j, const std::function<void(int
   }
 }
 
-void Solver::write_restart(const std::string& g, const std::string& ddv, const std::string& umean) {
+void Solver::write_restart(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t) {
   wait_checkpoint();
-  const RestartJob j = capture_restart(g, ddv, umean);
+  const RestartJob j = capture_restart(g, ddv, umean, t);
   // synchronous: the ranks take turns at device barriers
   write_restart_job(j, [this](int) { barrier(); });
   barrier();
 }
 
-void Solver::checkpoint_async(const std::string& g, const std::string& ddv, const std::string& umean) {
+void Solver::checkpoint_async(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t) {
   wait_checkpoint();
-  RestartJob j = capture_restart(g, ddv, umean);
+  RestartJob j = capture_restart(g, ddv, umean, t);
   const int P = plan_.P, rank = plan_.rank;
   const double timeout = comm_timeout_s_ > 0 ? comm_timeout_s_ : 3600.0;
   ckpt_thread_ = std::thread([this, j = std::move(j), P, rank, timeout]() {
@@ -2465,9 +2651,43 @@ void Solver::wait_checkpoint() {
   }
 }
 
-void Solver::read_restart(const std::string& g, const std::string& ddv, const std::string& umean) {
+// theta from a restart file of this grid (another grid is refused, as for G)
+void Solver::read_scalar_file(const std::string& path) {
+  CH_CHECK(sc_, "restart: a theta file needs scalar = true");
+  const Plan& p = plan_;
+  const int N = p.NY, NZ = p.NZ, lines = p.lines_loc();
+  const double N2 = static_cast<double>(p.NX) * p.Nzp;
+  std::vector<int> planes(p.nkx_loc);
+  for (int i = 0; i < p.nkx_loc; ++i) planes[i] = p.kx_fft_pos(p.kx0 + i);
+  {
+    auto at = h5_read_attrs(path);
+    CH_CHECK(!at.count("NX") || (static_cast<int>(at["NX"]) == p.NX && static_cast<int>(at["NY"]) == N && static_cast<int>(at["NZ"]) == NZ),
+             "restart file " << path << " is on the grid " << at["NX"] << "x" << at["NY"] << "x" << at["NZ"]
+                             << " (input.T must be on the solver's grid: the scalar is not regridded)");
+  }
+  std::vector<double> d;
+  int dims[3];
+  h5_read_planes(path, planes, d, dims);
+  CH_CHECK(dims[0] == p.NX && dims[1] == N && dims[2] == 2 * NZ,
+           "restart file " << path << " has dims " << dims[0] << "x" << dims[1] << "x" << dims[2]
+                           << " (input.T must be on the solver's grid: the scalar is not regridded)");
+  std::vector<std::complex<double>> th(canon_, 0.0);
+  for (int i = 0; i < p.nkx_loc; ++i)
+    for (int kzl = 0; kzl < p.nkz_loc; ++kzl)
+      for (int j = 0; j < N; ++j) {
+        const size_t o = ((static_cast<size_t>(i) * NZ + p.kz0 + kzl) * N + j) * 2;
+        th[static_cast<size_t>(j) * lines + i * p.nkz_loc + kzl] = std::complex<double>(d[o], d[o + 1]) / N2;
+      }
+  set_scalar(th.data());
+}
+
+void Solver::read_restart(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t) {
+  const bool with_t = !t.empty() && t != "-";
+  CH_CHECK(!with_t || sc_, "restart: a theta file needs scalar = true");
   if (cfg_.regrid) {  // files on any grid of the same box (regrid.cpp)
+    CH_CHECK(!with_t, "regrid with input.T: regridding the scalar is not supported");
     read_restart_regrid(g, ddv, umean, cfg_.regrid_stretch);
+    if (sc_) init_scalar_ic();
     return;
   }
   const Plan& p = plan_;
@@ -2518,9 +2738,11 @@ void Solver::read_restart(const std::string& g, const std::string& ddv, const st
   }
   set_state(phi.data(), om.data(), U.data());
   auto attrs = h5_read_attrs(g);
-  double t = attrs.count("time") ? attrs["time"] : 0.0, dt = attrs.count("dt") ? attrs["dt"] : 0.0;
-  set_time(t, dt);
+  const double tm = attrs.count("time") ? attrs["time"] : 0.0, dt = attrs.count("dt") ? attrs["dt"] : 0.0;
+  set_time(tm, dt);
   nstep_ = attrs.count("step") ? static_cast<long>(attrs["step"]) : 0;
+  if (with_t) read_scalar_file(t);
+  else if (sc_) init_scalar_ic();
 }
 
 }  // namespace channel

@@ -95,7 +95,7 @@ int main(int argc, char** argv) {
       std::printf("%s", cfg.to_string().c_str());
     }
     solver = std::make_unique<Solver>(cfg, pi.rank, pi.size, device, uid);
-    if (cfg.ic == "file") solver->read_restart(cfg.in_G, cfg.in_DDV, cfg.in_UMEAN);
+    if (cfg.ic == "file") solver->read_restart(cfg.in_G, cfg.in_DDV, cfg.in_UMEAN, cfg.scalar ? cfg.in_T : "-");
     else solver->init_ic();
     solver->prepare();
     const long n = steps >= 0 ? steps : cfg.nsteps;
@@ -105,7 +105,7 @@ int main(int argc, char** argv) {
     if (pi.rank == 0)
       std::printf("\nchannel_mi355x: %ld RK3 steps in %.3f s (%.3f ms/step, %.3e grid-pts/s)\n", n, sec,
                   n ? 1e3 * sec / n : 0.0, n ? double(cfg.NX) * cfg.NY * cfg.nzp() * n / sec : 0.0);
-    if (cfg.out_G != "-" && cfg.out_DDV != "-") solver->write_restart(cfg.out_G, cfg.out_DDV, cfg.out_UMEAN);
+    if (cfg.out_G != "-" && cfg.out_DDV != "-") solver->write_restart(cfg.out_G, cfg.out_DDV, cfg.out_UMEAN, cfg.scalar ? cfg.out_T : "-");
     solver.reset();
   } catch (const std::exception& e) {
     std::fprintf(stderr, "[rank %d] fatal: %s\n", pi.rank, e.what());

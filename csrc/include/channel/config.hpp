@@ -108,6 +108,15 @@ struct Config {
   // Restart onto another grid (regrid.hpp): the input files may be on any grid of the same box
   bool regrid = false;                 // false: a file on another grid is refused
   double regrid_stretch = 0.0;         // the input files' tanh stretching (0 = the file's "stretch" attribute, else `stretch`)
+  // Passive scalar (one rank without a communicator): d(theta)/dt = -div(u theta) + kappa lap(theta) + source,
+  // kappa = 1 / (Re Pr), Dirichlet walls; theta never acts on the flow
+  bool scalar = false;
+  double Pr = 0.71;                    // Prandtl (Schmidt) number, > 0
+  double scalar_lower = 0.0, scalar_upper = 0.0;  // Theta(-1), Theta(+1)
+  double scalar_source = 0.0;          // uniform source S added to d(Theta)/dt (internal heating)
+  std::string scalar_ic = "laminar";   // laminar (the steady conduction profile) | zero | file (implied by input.T)
+  std::string in_T = "-", out_T = "-"; // restart file of theta (layout, units and attributes of G)
+  int scalar_every = 0;                // 0 = off; TMEAN.dat, TRMS.dat, UT.dat, VT.dat, TWALL.dat
 
   static Config from_tree(const ConfigTree& t);
   static Config from_file(const std::string& path, const std::vector<std::string>& overrides = {});

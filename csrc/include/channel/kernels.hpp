@@ -154,6 +154,34 @@ struct PressureArgs {
 };
 void pressure_solve(const YTablesDev& t, const PressureArgs& a, bool fp64, hipStream_t stream);
 
+// ---- passive scalar (y-line advance of one RK3 substep) ----------------------------------------
+// Per line, all in fp64 (scalar.hip): N = -(i al Fx + D1 Fy + i be Fz) (mean line: Re N + source), R_n = M N,
+//   r = M th + dt [rk_a kappa (K th - k2 M th) + rk_g R_n + rk_z R_prev], wall rows of r zero (mean line:
+//   lower, upper), th_new = ((1 + c k2) M - c K, identity wall rows)^-1 r with c = rk_b dt kappa.
+// th is advanced in place and R_n stored over R_prev (store_r); the mean line's imaginary part, the padded
+// kz lines (local kz >= nkz_real) and the rows >= N of the blocked layout are written as zero.
+struct ScalarArgs {
+  int N = 0;              // NY
+  int lines = 0;          // local lines = nkx_loc * nkz, line = ikx_local * nkz + kz
+  int nkz = 0, nkz_real = 0, kx0 = 0, nkx = 0, Kx = 0;  // nkz = kz line stride (kzb: padded to 8)
+  int kzb = 0;            // spectral layout (spec_index)
+  int kz0 = 0;
+  double ax = 1, az = 2;  // 2 pi / LX, 2 pi / LZ
+  double kappa = 1.0;     // 1 / (Re Pr)
+  double rk_a = 0, rk_b = 0, rk_g = 0, rk_z = 0;
+  const double* dt = nullptr;  // device scalar
+  double lower = 0, upper = 0, source = 0;  // Theta(-1), Theta(+1), uniform source (mean line)
+  const void* fx = nullptr;   // (u theta)^, (v theta)^, (w theta)^ of the substep's state
+  const void* fy = nullptr;
+  const void* fz = nullptr;
+  void* th = nullptr;
+  void* Rth = nullptr;
+  int store_r = 1;        // 0: skip the R store (last substep: the next one has zeta = 0)
+  int lds_poison = 0;     // debug: fill the LDS with NaN before use
+  unsigned* health = nullptr;  // bit 0: non-finite state
+};
+void scalar_advance(const YTablesDev& t, const ScalarArgs& a, bool fp64, hipStream_t stream);
+
 // ---- FFT stages ---------------------------------------------------------------------------
 // Per-pass FFT twiddle tables for length n (FftPlan T1/T2 layout, fft_device.hpp), fp32 or fp64.
 struct Twiddles {
@@ -341,6 +369,19 @@ constexpr int kQuadRows = 8;    // sums of u'v over Q1..Q4, then their sample co
 constexpr int kHistMaxBins = 256, kHistMaxJoint = 64;  // the block's LDS tables (zreal refuses more)
 void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
 
+// z stage of the passive scalar: per row of an x-expanded chunk [4 fields][row][kz] (u, v, w, theta; the
+// layout zphys reads) the C2R transforms of the pairs (u, v) and (w, theta), the products u theta,
+// v theta, w theta in the storage precision, one forward transform of u theta + i v theta split by
+// conjugate symmetry and one of (w theta, 0); the retained kz (k < nkz), scaled by 1 / (NX Nzp), are
+// stored over fields 0..2 of the row.  A row loads its four inputs before it stores.
+struct ZScalarArgs {
+  int NX = 0, Nzp = 0, nkz = 0, ny = 0;   // rows = ny * NX
+  int xpitch = 0;                    // row pitch (0 = nkz)
+  long long field_stride = 0;        // element stride between the four fields
+  int lds_poison = 0;                // debug: fill the LDS with NaN before use
+};
+void zscalar(const ZScalarArgs& a, void* fields, const Twiddles& tw, bool fp64, hipStream_t s);
+
 // standalone FFT entry points for tests: batched C2C along the contiguous axis
 void fft_c2c_test(void* data, int n, int batch, int dir, const Twiddles& tw, bool fp64, hipStream_t s);
 
@@ -427,6 +468,14 @@ struct PStrainArgs : SpecWalkArgs {   // p and, in six-output mode, only u, v, w
   double* sums = nullptr;             // [kPStrainRows][N]
 };
 void pstrain_accumulate(const PStrainArgs& a, bool fp64, hipStream_t s);
+// Scalar plane sums: the Parseval products of the passive scalar theta (in the place of p) with itself and
+// the velocities of the current state, read once like the gradient sums (same walk, weights and masks)
+// and accumulated (+=) into sums[kScalarSumRows][N]: |theta|^2, Re(u theta*), Re(v theta*), Re(w theta*).
+constexpr int kScalarSumRows = 4;
+struct ScalarSumArgs : SpecWalkArgs {  // p = theta-hat and u, v, w
+  double* sums = nullptr;             // [kScalarSumRows][N]
+};
+void scalarsum_accumulate(const ScalarSumArgs& a, bool fp64, hipStream_t s);
 // One-dimensional spectra and co-spectra at every plane: one local block of spectral fields is read
 // once, like the gradient sums (same inputs, weights and masks: kz = 0 once, kz > 0 twice, the mean
 // line and the padded lines skipped; products and sums in double), and per plane the products are

@@ -66,6 +66,21 @@ class Solver {
   void set_state(const std::complex<double>* phi, const std::complex<double>* omega, const double* U);
   void get_state(std::complex<double>* phi, std::complex<double>* omega, double* U) const;
   void init_ic();      // config ic: random | laminar | zero (deterministic, independent of P)
+  // ---- passive scalar (cfg.scalar; one rank without a communicator) ----------------------------
+  // theta-hat in the canonical [y][kx][kz] layout of the state; its mean line (kx, kz) = (0, 0) holds the
+  // real mean profile Theta(y) itself.  set_scalar clears R_theta.
+  bool scalar_on() const { return sc_ != nullptr; }
+  void set_scalar(const std::complex<double>* th);
+  void get_scalar(std::complex<double>* th) const;
+  void init_scalar_ic();  // config scalar_ic: laminar | zero
+  // the flux pass alone on the current state: (u theta)^, (v theta)^, (w theta)^, canonical [3][y][kx][kz]
+  std::vector<std::complex<double>> scalar_flux_hat();
+  // [5][NY]: Theta, <theta'theta'>, <u'theta'>, <v theta'>, <w theta'> (Parseval plane sums of the retained
+  // modes with the weights and the mean-line skip of stats(); products and sums in double)
+  std::vector<double> scalar_sums();
+  // device time in ms of one substep's scalar work: [x-backward, zscalar, x-forward, scalar_kernel]
+  // (events on the compute stream; tools/scalar_cost.py).  The state is left as it was.
+  std::vector<double> scalar_timing();
   void prepare();      // fill the transform inputs from the state (K-SPEC mode 0)
 
   // ---- time stepping ---------------------------------------------------------------------
@@ -220,8 +235,9 @@ class Solver {
   std::vector<std::complex<double>> rotational_hat();
 
   // ---- restart files (reference-compatible, Appendix B) --------------------------------
-  void write_restart(const std::string& g, const std::string& ddv, const std::string& umean);
-  void read_restart(const std::string& g, const std::string& ddv, const std::string& umean);
+  // t: the restart file of theta (layout, units and attributes of G), "-" = none
+  void write_restart(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t = "-");
+  void read_restart(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t = "-");
   // ---- restart onto another grid (regrid.cpp; regrid.hpp has the semantics) ---------------
   // Files on any grid of the same box: modes map by index (truncated or zero-padded), every line is
   // interpolated along y on the device, U(y) with the same table on the host.  read_restart calls it
@@ -237,7 +253,7 @@ class Solver {
   std::vector<double> regrid_timing() const { return regrid_ms_; }
   // capture the state now (host copy) and write the files from a background thread; the next
   // checkpoint / wait_checkpoint() / run() end / destructor joins it (and rethrows its error)
-  void checkpoint_async(const std::string& g, const std::string& ddv, const std::string& umean);
+  void checkpoint_async(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t = "-");
   void wait_checkpoint();
 
   // ---- raw device access (tests / bindings) ----------------------------------------------
@@ -315,6 +331,14 @@ class Solver {
   void write_yspectra_files();
   void write_sbudget_files();
   void write_ycross_files();
+  void write_scalar_files();
+  // passive scalar: the flux pass of the stage state into the flux fields (before transforms(), which
+  // overwrites u, v, w with H) and the y-line advance of substep n (after K-SPEC; reads d_dt_).
+  // ms (eager, timing): += the device times of the x-backward, zscalar and x-forward launches
+  void scalar_flux_device(double* ms = nullptr);
+  void scalar_advance_device(int n);
+  void read_scalar_file(const std::string& path);  // theta from a restart file on this grid
+  void* scalar_ptr(int f) const { return static_cast<char*>(sc_) + static_cast<size_t>(f) * spec_ * esz_; }
   // p-hat' of the current state into field 1 of d_pres_ (device part of static_pressure_hat): the
   // pressure solve, then the return trip of r through physical space (static_return_device)
   void static_pressure_device();
@@ -342,7 +366,8 @@ class Solver {
   void for_kblocks(F&& fn) const;
   void reduce_fetch(double* d, size_t n, double* h);
   std::vector<int> all_planes() const;
-  XArgs pi_backward(const XArgs& xc, const XSrc& sc);
+  // field: the one spectral field transformed (default: Pi, field 0 of d_pres_); its mean line is kept
+  XArgs pi_backward(const XArgs& xc, const XSrc& sc, const void* field = nullptr);
   ZRealArgs zreal_args(int y0, int ny, int nf) const;
   template <typename Put>
   void export_fields(const std::vector<int>& planes, const std::vector<int>& fidx, Put&& put);
@@ -350,14 +375,14 @@ class Solver {
   void wait(hipStream_t s);           // stream sync with the communicator watchdog (P > 1)
   void invalidate_graphs();
   struct RestartJob {
-    std::string g, ddv, umean;
-    std::vector<std::complex<double>> phi, om;
+    std::string g, ddv, umean, t;
+    std::vector<std::complex<double>> phi, om, th;
     std::vector<double> U;
     double time = 0, dt = 0;
     long step = 0;
     long serial = 0;
   };
-  RestartJob capture_restart(const std::string& g, const std::string& ddv, const std::string& umean);
+  RestartJob capture_restart(const std::string& g, const std::string& ddv, const std::string& umean, const std::string& t);
   // turn(t) is called before every rank-ordered write step t (t % P = the writing rank)
   void write_restart_job(const RestartJob& j, const std::function<void(int)>& turn);
   // a regrid source: its grid and units, and fill(field 0 phi | 1 omega, local target kx of a batch,
@@ -391,6 +416,8 @@ class Solver {
   void* state_ = nullptr;  // phi, omega, Rphi, Romega (4 * spec)
   void* out_ = nullptr;    // 6 * spec
   void* phys_ = nullptr;   // 6 * phys
+  void* sc_ = nullptr;     // passive scalar (cfg.scalar): theta, R_theta, F_x, F_y, F_z (5 * spec)
+  double* d_ssum_ = nullptr;  // scalar sums: [kScalarSumRows][NY]
   void* xbuf_ = nullptr;   // P>1: 6 * ny_loc*nkx*nkz_loc (A-exchange blocks)
   hipEvent_t ev_dtf_[2] = {nullptr, nullptr};  // P = 1 one-chunk path: dt update forked beside the x-forward
   unsigned* d_rowtab_ = nullptr;  // slab P > 1: per retained kx row, its exchange segment's offset / stride (XSrc::rowtab)

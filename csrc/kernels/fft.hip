@@ -258,6 +258,19 @@ void zreal(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool fp64
   HIP_LAUNCH_CHECK(s);
 }
 
+void zscalar(const ZScalarArgs& a_in, void* fields, const Twiddles& tw, bool fp64, hipStream_t s) {
+  ZScalarArgs a = a_in;
+  if (lds_poison_enabled()) a.lds_poison = 1;
+  CH_CHECK(tw.n == a.Nzp && tw.fp64 == fp64, "zscalar: twiddle table mismatch");
+  CH_CHECK(a.nkz == a.Nzp / 3 + 1, "zscalar: one segment of the 2/3 rule's retained kz (Nzp/3 + 1)");
+  CH_CHECK(a.xpitch == 0 || a.xpitch >= a.nkz, "zscalar: a row pitch below nkz");
+  CH_CHECK(a.NX > 0 && a.ny >= 0 && fields, "zscalar: empty");
+  CH_CHECK(a.field_stride >= static_cast<long long>(a.ny) * a.NX * (a.xpitch ? a.xpitch : a.nkz), "zscalar: the fields overlap");
+  if (a.ny == 0) return;
+  CH_DISPATCH_N(a.Nzp, fft_zs_len<NN>(a, fields, tw, fp64, s));
+  HIP_LAUNCH_CHECK(s);
+}
+
 void fft_c2c_test(void* data, int n, int batch, int dir, const Twiddles& tw, bool fp64, hipStream_t s) {
   CH_CHECK(tw.n == n && tw.fp64 == fp64, "fft_c2c_test: twiddle table mismatch");
   CH_DISPATCH_N(n, fft_test_len<NN>(data, batch, dir, tw, fp64, s));

@@ -2379,6 +2379,139 @@ static void zreal_launch(const ZRealArgs& a, const void* fields, const Twiddles&
                        static_cast<const T2*>(fields), static_cast<const T2*>(tw.buf));
 }
 
+// ---- z stage of the passive scalar (kernels.hpp ZScalarArgs) -----------------------------------
+// The row geometry and the pair transforms of zreal_kernel, and its return trip three times over: the
+// pair (u, v) stays in registers (as PRES keeps ku, kv) while (w, theta) is transformed; the products
+// u theta, v theta go back into the LDS slots their factors were read from as Z = u theta + i v theta
+// and w theta waits in registers; Z is forward transformed and split by conjugate symmetry, F_x[k] =
+// (Z[k] + conj Z[N - k]) / 2, F_y[k] = (Z[k] - conj Z[N - k]) / (2 i); then (w theta, 0) takes the same
+// trip.  The retained kz of the three, scaled by 1 / (NX Nzp), go over fields 0..2 of the row: all four
+// inputs of the row were loaded before the first forward transform.  One row group per block.
+template <int NZP, typename T>
+__global__ void __launch_bounds__((zphys_rows<NZP, T>() * zphys_tpr<NZP>(sizeof(T))))
+    zscalar_kernel(ZScalarArgs a, typename C2<T>::type* fields, const typename C2<T>::type* tw) {
+  using T2 = typename C2<T>::type;
+  constexpr int TPR = zphys_tpr<NZP>(sizeof(T)), ZWT = zphys_rows<NZP, T, TPR>(), NT = ZWT * TPR;
+  constexpr int PITCH = FftPitch<NZP>::value;
+  constexpr int TPRF = TPR < 64 ? 64 : TPR;     // threads per transform call (one wave or a row)
+  constexpr int RWW = TPR < 64 ? 64 / TPR : 1;  // rows per transform call
+  constexpr int TS = FftPlan<NZP>::TSIZE;
+  constexpr int nkz = NZP / 3 + 1, Kz = nkz - 1;  // (checked on the host)
+  constexpr int MK = (nkz + TPR - 1) / TPR;
+  constexpr int VEC = 16 / sizeof(T), NV = NZP / VEC, EV = (NV + TPR - 1) / TPR;
+  static_assert(NZP % VEC == 0, "rows of whole 16-byte pieces");
+  __shared__ T2 s[ZWT * PITCH];
+  __shared__ T2 tws[TS];
+  const int tid = threadIdx.x, t = tid % TPR, w = tid / TPR;
+  if (a.lds_poison) {
+    lds_poison_fill(s, sizeof(s));
+    lds_poison_fill(tws, sizeof(tws));
+    __syncthreads();
+  }
+  for (int i = tid; i < TS; i += NT) tws[i] = tw[i];
+  __syncthreads();
+  T2* row = s + w * PITCH;
+  T2* frow = s + (tid / TPRF) * RWW * PITCH;  // first row of this thread's transform group
+  const int ft = tid % TPRF;
+  const long long nrows = static_cast<long long>(a.ny) * a.NX;
+  const long long r = static_cast<long long>(blockIdx.x) * ZWT + w;
+  // rows past the end run the transforms on zeros (the barriers are block-uniform) and touch no
+  // global memory beyond clamped loads
+  const bool rv = r < nrows;
+  const long long rc = rv ? r : nrows - 1;
+  const long long rowp = a.xpitch ? a.xpitch : nkz;
+  RVec<T> ku[EV], kv[EV], kw[EV];  // u, v of the first pair; then w theta
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const T2* A = fields + (2 * p) * a.field_stride + rc * rowp;
+    const T2* B = fields + (2 * p + 1) * a.field_stride + rc * rowp;
+    // unconditional loads at a clamped (in-bounds) index, zeros selected afterwards; Z_k = A_k + i B_k,
+    // Z_{N-k} = conj(A_k) + i conj(B_k), the kz = 0 imaginary parts dropped, zeros between
+#pragma unroll
+    for (int i = 0; i < MK; ++i) {
+      const int k = t + TPR * i;
+      const T2 x = A[min(k, Kz)], y = B[min(k, Kz)];
+      const T2 va = rv ? x : T2{0, 0}, vb = rv ? y : T2{0, 0};
+      if (k < nkz) {
+        if (k == 0) {
+          row[fft_pidx(0)] = T2{va.x, vb.x};
+        } else {
+          row[fft_pidx(k)] = T2{va.x - vb.y, va.y + vb.x};
+          row[fft_pidx(NZP - k)] = T2{va.x + vb.y, vb.x - va.y};
+        }
+      }
+    }
+    for (int k = Kz + 1 + t; k < NZP - Kz; k += TPR) row[fft_pidx(k)] = T2{0, 0};
+    row_sync<TPRF>();
+    wave_fft<NZP, RWW, PITCH, true, TPRF>(frow, tws, ft);
+#pragma unroll
+    for (int i = 0; i < EV; ++i) {
+      const int nv = t + TPR * i;
+      if (NV % TPR == 0 || nv < NV) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const T2 z = row[fft_pidx(nv * VEC + j)];
+          if (p == 0) {
+            ku[i].v[j] = z.x;
+            kv[i].v[j] = z.y;
+          } else {  // z = (w, theta): the products in the storage precision, as zphys forms H
+            row[fft_pidx(nv * VEC + j)] = T2{ku[i].v[j] * z.y, kv[i].v[j] * z.y};
+            kw[i].v[j] = z.x * z.y;
+          }
+        }
+      }
+    }
+    row_sync<TPRF>();  // this pair's LDS reads precede the next writes; p = 1: Z is in place
+  }
+  const T sc = static_cast<T>(1.0 / (static_cast<double>(a.NX) * NZP));
+  const T hs = sc * T(0.5);
+  wave_fft<NZP, RWW, PITCH, false, TPRF>(frow, tws, ft);
+  T2* O0 = fields + rc * rowp;
+  T2* O1 = fields + a.field_stride + rc * rowp;
+  T2* O2 = fields + 2 * a.field_stride + rc * rowp;
+#pragma unroll
+  for (int i = 0; i < MK; ++i) {
+    const int k = t + TPR * i;
+    if (k < nkz) {
+      const T2 zk = row[fft_pidx(k)], zn = row[fft_pidx(k == 0 ? 0 : NZP - k)];
+      if (rv) {
+        O0[k] = T2{(zk.x + zn.x) * hs, (zk.y - zn.y) * hs};
+        O1[k] = T2{(zk.y + zn.y) * hs, (zn.x - zk.x) * hs};
+      }
+    }
+  }
+  row_sync<TPRF>();  // the split's reads precede the writes of (w theta, 0)
+#pragma unroll
+  for (int i = 0; i < EV; ++i) {
+    const int nv = t + TPR * i;
+    if (NV % TPR == 0 || nv < NV) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) row[fft_pidx(nv * VEC + j)] = T2{kw[i].v[j], T(0)};
+    }
+  }
+  row_sync<TPRF>();
+  wave_fft<NZP, RWW, PITCH, false, TPRF>(frow, tws, ft);
+#pragma unroll
+  for (int i = 0; i < MK; ++i) {
+    const int k = t + TPR * i;
+    if (rv && k < nkz) {
+      const T2 z = row[fft_pidx(k)];
+      O2[k] = T2{z.x * sc, z.y * sc};
+    }
+  }
+}
+
+template <int NN, typename T>
+static void zscalar_launch(const ZScalarArgs& a, void* fields, const Twiddles& tw, hipStream_t s) {
+  using T2 = typename C2<T>::type;
+  constexpr int ZR = zphys_rows<NN, T>(), TPR = zphys_tpr<NN>(sizeof(T));
+  const long long nrows = static_cast<long long>(a.ny) * a.NX;
+  const long long ngroups = (nrows + ZR - 1) / ZR;
+  CH_CHECK(ngroups < (1LL << 31), "zscalar: too many rows for one launch");
+  hipLaunchKernelGGL((zscalar_kernel<NN, T>), dim3(static_cast<unsigned>(ngroups)), dim3(ZR * TPR), 0, s, a,
+                     static_cast<T2*>(fields), static_cast<const T2*>(tw.buf));
+}
+
 // ---- standalone batched C2C (tests) ----------------------------------------------------------
 template <int N, typename T, bool INV>
 __global__ void __launch_bounds__(256) fft_test_kernel(typename C2<T>::type* data, int batch,
@@ -2443,6 +2576,11 @@ void fft_zr_len(const ZRealArgs& a, const void* fields, const Twiddles& tw, bool
   else zreal_launch<NN, float>(a, fields, tw, s);
 }
 template <int NN>
+void fft_zs_len(const ZScalarArgs& a, void* fields, const Twiddles& tw, bool fp64, hipStream_t s) {
+  if (fp64) zscalar_launch<NN, double>(a, fields, tw, s);
+  else zscalar_launch<NN, float>(a, fields, tw, s);
+}
+template <int NN>
 void fft_test_len(void* data, int batch, int dir, const Twiddles& tw, bool fp64, hipStream_t s) {
   dim3 grid((batch + 3) / 4);
   if (fp64) {
@@ -2469,6 +2607,7 @@ void fft_test_len(void* data, int batch, int dir, const Twiddles& tw, bool fp64,
   template void fft_xf_len<NN>(const XArgs&, const void*, const XDst&, const Twiddles&, bool, hipStream_t); \
   template void fft_zp_len<NN>(const ZArgs&, void*, const Twiddles&, bool, hipStream_t);                    \
   template void fft_zr_len<NN>(const ZRealArgs&, const void*, const Twiddles&, bool, hipStream_t);          \
+  template void fft_zs_len<NN>(const ZScalarArgs&, void*, const Twiddles&, bool, hipStream_t);              \
   template void fft_test_len<NN>(void*, int, int, const Twiddles&, bool, hipStream_t);
 // (extern declarations per entry point: an extern template covers one declaration)
 #define CH_FFT_EXTERN_ALL(NN)                                                                                   \
@@ -2476,6 +2615,7 @@ void fft_test_len(void* data, int batch, int dir, const Twiddles& tw, bool fp64,
   extern template void fft_xf_len<NN>(const XArgs&, const void*, const XDst&, const Twiddles&, bool, hipStream_t); \
   extern template void fft_zp_len<NN>(const ZArgs&, void*, const Twiddles&, bool, hipStream_t);                    \
   extern template void fft_zr_len<NN>(const ZRealArgs&, const void*, const Twiddles&, bool, hipStream_t);          \
+  extern template void fft_zs_len<NN>(const ZScalarArgs&, void*, const Twiddles&, bool, hipStream_t);              \
   extern template void fft_test_len<NN>(void*, int, int, const Twiddles&, bool, hipStream_t);
 CH_FFT_POW2_LENGTHS(CH_FFT_EXTERN_ALL)
 CH_FFT_R3_LENGTHS(CH_FFT_EXTERN_ALL)
