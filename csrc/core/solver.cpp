@@ -330,6 +330,20 @@ void Solver::alloc() {
   d_health_ = reinterpret_cast<unsigned*>(d_max_ + 4);
   d_kprof_ = reinterpret_cast<unsigned long long*>(static_cast<char*>(dscal_) + nd * sizeof(double) + 32);
   kprof_on_ = std::getenv("CHANNEL_KSPEC_PROF") != nullptr;
+  {
+    // K-SPEC's statistics partials: one row of slots per workgroup of its largest resident grid
+    // (1024x385x1024: 256 x 1792 doubles, 3.7 MB), sized here and not on the launch path
+    SpecArgs q;
+    q.N = N;
+    q.out6 = combine_ ? 0 : 1;
+    q.explicit_dd = cfg_.explicit_d2 == "dd";
+    q.analytic_influence = cfg_.influence == "analytic";
+    stats_blocks_ = kspec_grid_capacity(ytab_, q, fp64_);
+    stats_stride_ = 4 * 64 * ytab_.R * ytab_.H;
+    const size_t pb = static_cast<size_t>(stats_blocks_) * stats_stride_ * sizeof(double);
+    HIP_CHECK(hipMalloc(&d_stats_part_, pb));
+    HIP_CHECK(hipMemset(d_stats_part_, 0, pb));
+  }
   // y planes per x->z->x chunk (P = 1): 16 planes of 6 fp32 fields at NX = Nzp = 1024 are ~270 MB,
   // about the Infinity Cache; measured 57.9 -> 52.3 ms/step at 1024x385x1024 (4..64 swept, 16 best
   // on one stream); alternating two streams with 8-plane chunks: 50.6 ms/step.  The chunk is sized
@@ -469,6 +483,8 @@ void Solver::free_all() {
                   static_cast<void*>(d_grad_), d_pres_, static_cast<void*>(d_pmom_), static_cast<void*>(d_pstr_),
                   static_cast<void*>(d_yspec_), d_hist_, static_cast<void*>(d_sbud_), static_cast<void*>(d_ycross_)})
     if (p) (void)hipFree(p);
+  if (d_stats_part_) (void)hipFree(d_stats_part_);
+  d_stats_part_ = nullptr;
   sc_ = nullptr;
   d_ssum_ = nullptr;
   d_pstr_ = nullptr;
@@ -796,13 +812,17 @@ void Solver::kspec(int mode, int n, bool stats) {
   a.Rphi = field_ptr(RPHI);
   a.Romega = field_ptr(ROMEGA);
   for (int i = 0; i < 6; ++i) a.out[i] = field_ptr(OUT0 + i);
-  a.stats = stats ? d_stats_ : nullptr;
+  a.stats_part = stats ? d_stats_part_ : nullptr;
+  a.stats_stride = stats_stride_;
+  a.stats_blocks = stats_blocks_;
   a.mean_diag = p.owns_mean() ? d_mean_ : nullptr;
   a.health = cfg_.health_check ? d_health_ : nullptr;
   a.prof = kprof_on_ ? d_kprof_ : nullptr;
   a.lds_poison = lds_poison_enabled() ? 1 : 0;
   a.out6 = combine_ ? 0 : 1;
-  if (stats) HIP_CHECK(hipMemsetAsync(d_stats_, 0, 4 * p.NY * sizeof(double), s_comp_));
+  // the workgroups' partial sums start from zero; every launch of this substep adds to them
+  if (stats)
+    HIP_CHECK(hipMemsetAsync(d_stats_part_, 0, static_cast<size_t>(stats_blocks_) * stats_stride_ * sizeof(double), s_comp_));
   ev(0, false);
   // (measured r2s: splitting this fused pass into an advance kernel and a prepare kernel frees no
   // occupancy at R = 7 -- 481 and 348 registers -- and costs 10.2 vs 7.2 ms per substep)
@@ -830,6 +850,8 @@ void Solver::kspec(int mode, int n, bool stats) {
     }
     fwd_pending_ = false;  // (the last wait joined the comm stream's forward exchange back)
   }
+  // plane sums from the partials, in workgroup order (every plane is written: d_stats_ needs no memset)
+  if (stats) kspec_stats_reduce(ytab_, d_stats_part_, stats_stride_, stats_blocks_, d_stats_, s_comp_);
   ev(0, true);
   if (stats && comm_) {
     HIP_CHECK(hipEventRecord(ev_stats_, s_comp_));

@@ -120,13 +120,25 @@ struct SpecArgs {
   int store_r = 1;        // 0: skip the R_phi/R_omega stores (last substep: the next one has zeta = 0)
   int lds_poison = 0;     // debug: fill the LDS with NaN before use (CHANNEL_LDS_POISON)
   // diagnostics
-  double* stats = nullptr;   // [4][N] plane sums (uu, vv, ww, uv) when non-null
+  // plane statistics when stats_part is non-null: workgroup b adds its tiles' sums (uu, vv, ww, uv)
+  // to row b of stats_part [stats_blocks][stats_stride] (zeroed by the caller, accumulated over the
+  // launches of a substep); kspec_stats_reduce forms the [4][N] plane sums from it.  stats_stride
+  // is the slot count 4 * 64 R H of the tables (a compile-time constant in the kernels) and
+  // stats_blocks >= the grid (kspec_grid_capacity): both checked at the launch.
+  double* stats_part = nullptr;
+  int stats_stride = 0, stats_blocks = 0;
   double* mean_diag = nullptr;  // [3N + 8]: U, Nx, dU/dy(walls), flux, pressure gradient ...
   unsigned* health = nullptr;   // bit 0: non-finite state
   unsigned long long* prof = nullptr;  // [kKspecPhases] shader-clock sums per phase (debug, CHANNEL_KSPEC_PROF)
 };
 constexpr int kKspecPhases = 10;
 void kspec_launch(const YTablesDev& t, const SpecArgs& a, bool fp64, hipStream_t stream);
+// the largest grid (workgroups) kspec_launch runs for these tables and arguments (the switches of
+// the environment included): the rows SpecArgs::stats_part needs
+int kspec_grid_capacity(const YTablesDev& t, const SpecArgs& a, bool fp64);
+// stats[4][N] = the sum over rows 0 .. blocks-1, in that order, of part[blocks][stride], each slot
+// mapped to the plane it stands for (kspec_kernel's row map for t.R, t.H)
+void kspec_stats_reduce(const YTablesDev& t, const double* part, int stride, int blocks, double* stats, hipStream_t stream);
 // kernel name(s) of this thread's last K-SPEC launch in rocprofv3's kernel-name form, template
 // arguments R, T, W, NS, XM, PAR, GLM, SPLIT, H ("kspec_kernel<7, float, 4, 2, 2, 0, 0, 0, 1>"); the
 // split (CHANNEL_KSPEC_SPLIT=1) reads "kspec_kernel<..., 1, 1> + kspec_out_kernel<R, T, W, XM>" (tests)

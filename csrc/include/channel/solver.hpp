@@ -439,6 +439,11 @@ class Solver {
   double* d_dtlog_ = nullptr;
   float* d_max_ = nullptr;
   double* d_stats_ = nullptr;
+  // K-SPEC's per-workgroup partial plane sums [stats_blocks_][stats_stride_] (SpecArgs::stats_part):
+  // one row per workgroup of the largest K-SPEC grid, reduced into d_stats_ after the statistics
+  // substep's last launch
+  double* d_stats_part_ = nullptr;
+  int stats_blocks_ = 0, stats_stride_ = 0;
   double* d_mean_ = nullptr;
   unsigned* d_health_ = nullptr;
   unsigned long long* d_kprof_ = nullptr;

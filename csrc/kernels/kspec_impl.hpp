@@ -488,9 +488,11 @@ __global__ void __launch_bounds__(W * 64 * H) kspec_kernel(YTab tg, SpecArgs a) 
   for (int i = threadIdx.x; i < NTILES * St::TILE; i += NT) tile_mem[i] = T2{0, 0};
   __syncthreads();
   const Xl<XM> xl{xs_mem + wv * XS};
-  // statistics reduction [4][64 R] in the staging tiles: between the phi store and the output
-  // stores nothing reads them, and the output stores rewrite every slot a column read uses
-  // (padding rows included, with zeros) before the next staging
+  // statistics reduction of a tile's W lines, [4][ROWS] slots (slot (h R + r) 64 + lane holds row
+  // h HR + lane R + r), in the staging tiles: between the phi store and the output stores nothing
+  // reads them, and the output stores rewrite every slot a column read uses (padding rows included,
+  // with zeros) before the next staging.  The tile sums go to this workgroup's row of
+  // SpecArgs::stats_part (no global atomics); kspec_stats_reduce maps the slots to rows.
   double* sred = reinterpret_cast<double*>(tile_mem);
   static_assert(St::TILE * sizeof(T2) >= 4 * ROWS * sizeof(double), "tile too small for the statistics reduction");
 
@@ -969,10 +971,21 @@ __global__ void __launch_bounds__(W * 64 * H) kspec_kernel(YTab tg, SpecArgs a) 
       re = -bi;
       im = br;
     };
-    // plane statistics (statistics.cu:7-95), fluctuations only, weight 2 for kz > 0
-    if (a.stats) {
+    // plane statistics (statistics.cu:7-95), fluctuations only, weight 2 for kz > 0, as per-workgroup
+    // partial sums: slot i of this workgroup's row of a.stats_part is loaded into sred[i] by thread
+    // i % NT, the tile's W lines are added to it in LDS, and the same thread stores it back.  The
+    // slot is that thread's alone for the whole launch (and the other launches of the substep, kx
+    // sub-blocks), so a plain load + add + store, no global atomic; kspec_stats_reduce sums the rows
+    // in workgroup order afterwards.  The row stride is the slot count (SpecArgs::stats_stride,
+    // checked at the launch).  Both copies one slot at a time (rolled): this is where the kernel's
+    // register pressure peaks, and every value held across the LDS sums (the partials loaded ahead,
+    // to hide their L2 latency behind the barrier) is a register more for the whole kernel: 412
+    // instead of 396 VGPRs + AGPRs at R = 7 fp32 with the 7 slots of a thread held, 394 this way.
+    if (a.stats_part) {
+      double* const part = a.stats_part + static_cast<size_t>(blockIdx.x) * (4 * ROWS);
       __syncthreads();  // every wave is done with the tiles (last use: the phi store or the omega column)
-      for (int i = threadIdx.x; i < 4 * ROWS; i += NT) sred[i] = 0.0;
+#pragma unroll 1
+      for (int i = threadIdx.x; i < 4 * ROWS; i += NT) sred[i] = part[i];
       __syncthreads();
       if (valid && !is_mean) {
         const double wgt = kz == 0 ? 1.0 : 2.0;
@@ -989,11 +1002,8 @@ __global__ void __launch_bounds__(W * 64 * H) kspec_kernel(YTab tg, SpecArgs a) 
         }
       }
       __syncthreads();
-      for (int i = threadIdx.x; i < 4 * ROWS; i += NT) {
-        const int s = i / ROWS, rem = i - s * ROWS, hr = rem / 64, l = rem - hr * 64;
-        const int j = (hr / R) * HR + l * R + hr % R;
-        if (j < N) atomicAdd(&a.stats[s * N + j], sred[i]);
-      }
+#pragma unroll 1
+      for (int i = threadIdx.x; i < 4 * ROWS; i += NT) part[i] = sred[i];
       __syncthreads();  // sred is a staging tile again
     }
     KSPEC_STAMP(8)
@@ -1211,9 +1221,12 @@ __global__ void __launch_bounds__(W * 64) kspec_out_kernel(YTab tg, SpecArgs a) 
       re = -bi;
       im = br;
     };
-    if (a.stats) {
+    if (a.stats_part) {  // (per-workgroup partial sums, as in kspec_kernel)
+      constexpr int NT = W * 64;
+      double* const part = a.stats_part + static_cast<size_t>(blockIdx.x) * (4 * ROWS);
       __syncthreads();
-      for (int i = threadIdx.x; i < 4 * ROWS; i += W * 64) sred[i] = 0.0;
+#pragma unroll 1
+      for (int i = threadIdx.x; i < 4 * ROWS; i += NT) sred[i] = part[i];
       __syncthreads();
       if (valid && !is_mean) {
         const double wgt = kz == 0 ? 1.0 : 2.0;
@@ -1230,11 +1243,8 @@ __global__ void __launch_bounds__(W * 64) kspec_out_kernel(YTab tg, SpecArgs a) 
         }
       }
       __syncthreads();
-      for (int i = threadIdx.x; i < 4 * ROWS; i += W * 64) {
-        const int s = i / ROWS, rem = i - s * ROWS, r = rem / 64, l = rem - r * 64;
-        const int j = l * R + r;
-        if (j < N) atomicAdd(&a.stats[s * N + j], sred[i]);
-      }
+#pragma unroll 1
+      for (int i = threadIdx.x; i < 4 * ROWS; i += NT) part[i] = sred[i];
       __syncthreads();
     }
     st.store(static_cast<T2*>(a.out[0]), d[0], d[1]);
@@ -1340,8 +1350,24 @@ inline void kspec_note_variant(int W, int NS, int PAR, int GLM = 0, int SPLIT = 
   kspec_variant_slot() = KspecVariant{R, W, NS, static_cast<int>(kspec_xmode<R, T>()), PAR, GLM, SPLIT, H, W2, sizeof(T) == 8};
 }
 
+// With `cap` non-null nothing is launched: the variants chosen for these tables and arguments only
+// report the largest persistent grid they would launch (kspec_grid_capacity, the rows of
+// SpecArgs::stats_part).
 template <int R, typename T, int PAR = 0>
-static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t stream) {
+static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t stream, int* cap) {
+  // one kernel on its persistent grid: as many blocks as can be resident at once, each walking
+  // tiles of `lines` lines
+  auto go = [&](auto k, int lines, int threads) {
+    const int resident = resident_blocks(reinterpret_cast<const void*>(k), threads);
+    if (cap) {
+      *cap = std::max(*cap, resident);
+      return;
+    }
+    const int grid = std::min((a.lines + lines - 1) / lines, resident);
+    CH_CHECK(!a.stats_part || (grid <= a.stats_blocks && a.stats_stride == 4 * 64 * R * t.H),
+             "kspec: the statistics partial buffer does not fit the grid (rows) or the line (slots per row)");
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), 0, stream, t.tab, a);
+  };
   if constexpr (R == 3 && PAR == 0) {
     if (const int v = kspec_var_env()) {
       constexpr int W3 = 4;
@@ -1351,9 +1377,7 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
                         : kspec_kernel<3, T, 8, 2, kspec_xmode<3, T>(), 0>;
       const int w = v == 1 ? W3 : 8;
       kspec_note_variant<3, T>(w, v == 1 ? 1 : (v == 3 ? 7 : (v == 4 ? 5 : 2)), 0);
-      const int nt = (a.lines + w - 1) / w;
-      dim3 grid(std::min(nt, resident_blocks(reinterpret_cast<const void*>(k), w * 64))), block(w * 64);
-      hipLaunchKernelGGL(k, grid, block, 0, stream, t.tab, a);
+      go(k, w, w * 64);
       return;
     }
   }
@@ -1363,9 +1387,7 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
       constexpr int W2 = 4;
       auto k = kspec_kernel<4, float, W2, kspec_slots<4, float>(), kspec_xmode<4, float>(), PAR, 0, 0, 2>;
       kspec_note_variant<4, float>(W2, kspec_slots<4, float>(), PAR, 0, 0, 2);
-      const int nt = (a.lines + W2 - 1) / W2;
-      dim3 grid(std::min(nt, resident_blocks(reinterpret_cast<const void*>(k), W2 * 128))), block(W2 * 128);
-      hipLaunchKernelGGL(k, grid, block, 0, stream, t.tab, a);
+      go(k, W2, W2 * 128);
       return;
     }
   }
@@ -1387,9 +1409,7 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
       constexpr int W8 = 8;
       auto k = kspec_kernel<R, T, W8, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR, 1>;
       kspec_note_variant<R, T>(W8, kspec_slots<R, T>(), PAR, 1);
-      const int nt = (a.lines + W8 - 1) / W8;
-      dim3 grid(std::min(nt, resident_blocks(reinterpret_cast<const void*>(k), W8 * 64))), block(W8 * 64);
-      hipLaunchKernelGGL(k, grid, block, 0, stream, t.tab, a);
+      go(k, W8, W8 * 64);
       return;
     }
   }
@@ -1399,41 +1419,34 @@ static void kspec_launch_t(const YTablesDev& t, const SpecArgs& a, hipStream_t s
     if (sp == 1 && !a.out6) {  // (the output kernel writes the combine outputs)
       kspec_note_variant<R, T>(W, kspec_slots<R, T>(), PAR, 0, 1, 1, kspec_out_lines<R, T>());
       auto k1 = kspec_kernel<R, T, W, kspec_slots<R, T>(), kspec_xmode<R, T>(), PAR, 0, 1>;
-      const int nt1 = (a.lines + W - 1) / W;
-      dim3 g1(std::min(nt1, resident_blocks(reinterpret_cast<const void*>(k1), W * 64))), b1(W * 64);
-      hipLaunchKernelGGL(k1, g1, b1, 0, stream, t.tab, a);
+      go(k1, W, W * 64);
       constexpr int W2 = kspec_out_lines<R, T>();
       auto k2 = kspec_out_kernel<R, T, W2, kspec_xmode<R, T>()>;
-      const int nt2 = (a.lines + W2 - 1) / W2;
-      dim3 g2(std::min(nt2, resident_blocks(reinterpret_cast<const void*>(k2), W2 * 64))), b2(W2 * 64);
-      hipLaunchKernelGGL(k2, g2, b2, 0, stream, t.tab, a);
+      go(k2, W2, W2 * 64);
       return;
     }
   }
   kspec_note_variant<R, T>(W, ns, PAR, glm);
-  // persistent grid: as many blocks as can be resident at once
-  const int ntiles = (a.lines + W - 1) / W;
-  dim3 grid(std::min(ntiles, resident_blocks(reinterpret_cast<const void*>(kern), W * 64))), block(W * 64);
-  hipLaunchKernelGGL(kern, grid, block, 0, stream, t.tab, a);
+  go(kern, W, W * 64);
 }
 
 // all rows-per-lane and storage instantiations of one parity variant
 template <int PAR>
-void kspec_launch_par(const YTablesDev& t, const SpecArgs& a, bool fp64, hipStream_t stream) {
+void kspec_launch_par(const YTablesDev& t, const SpecArgs& a, bool fp64, hipStream_t stream, int* cap) {
 #ifdef CH_KSPEC_ISA_ONLY  // one instantiation, for ISA inspection builds
   CH_CHECK(t.R == CH_KSPEC_ISA_ONLY && !fp64, "ISA build");
-  kspec_launch_t<CH_KSPEC_ISA_ONLY, float, PAR>(t, a, stream);
+  kspec_launch_t<CH_KSPEC_ISA_ONLY, float, PAR>(t, a, stream, cap);
 #else
   if (fp64) {
-    CH_DISPATCH_R(t.R, (kspec_launch_t<R, double, PAR>(t, a, stream)));
+    CH_DISPATCH_R(t.R, (kspec_launch_t<R, double, PAR>(t, a, stream, cap)));
   } else {
-    CH_DISPATCH_R(t.R, (kspec_launch_t<R, float, PAR>(t, a, stream)));
+    CH_DISPATCH_R(t.R, (kspec_launch_t<R, float, PAR>(t, a, stream, cap)));
   }
 #endif
 }
-extern template void kspec_launch_par<0>(const YTablesDev&, const SpecArgs&, bool, hipStream_t);
-extern template void kspec_launch_par<1>(const YTablesDev&, const SpecArgs&, bool, hipStream_t);
-extern template void kspec_launch_par<2>(const YTablesDev&, const SpecArgs&, bool, hipStream_t);
-extern template void kspec_launch_par<3>(const YTablesDev&, const SpecArgs&, bool, hipStream_t);
+extern template void kspec_launch_par<0>(const YTablesDev&, const SpecArgs&, bool, hipStream_t, int*);
+extern template void kspec_launch_par<1>(const YTablesDev&, const SpecArgs&, bool, hipStream_t, int*);
+extern template void kspec_launch_par<2>(const YTablesDev&, const SpecArgs&, bool, hipStream_t, int*);
+extern template void kspec_launch_par<3>(const YTablesDev&, const SpecArgs&, bool, hipStream_t, int*);
 
 }  // namespace channel

@@ -3,6 +3,6 @@
 
 namespace channel {
 
-template void kspec_launch_par<1>(const YTablesDev&, const SpecArgs&, bool, hipStream_t);
+template void kspec_launch_par<1>(const YTablesDev&, const SpecArgs&, bool, hipStream_t, int*);
 
 }  // namespace channel
